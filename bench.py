@@ -18,8 +18,8 @@ processes over RCCL); the replica throughput (one independent proof per GPU)
 is reported beside it as `replicas`, and is the value only if the one-proof
 run failed (the line says so).
 
-The same line carries the Goldilocks NTT number of the metric, measured in the
-same process after the proofs: the LDE of configs[1] (2^23 -> 2^24 x 100
+Under --full the same line carries the Goldilocks NTT number of the metric,
+measured in the same process after the proofs: the LDE of configs[1] (2^23 -> 2^24 x 100
 columns, extendPol, starks.cpp:53), as `lde` (Gelem/s) -- and the LDE is the
 kernel chain `roofline` describes (algorithmic bytes per LDE =
 24 N C; achieved = that / the device time of the LDE's NTT passes, HIP events
@@ -27,12 +27,28 @@ on the launch stream).  Poseidon Merkle hashing, the largest share of the
 proof, is integer-VALU bound; `valu` prices its kernel against the measured
 issue peak (tools/instbench.hip, profiles/*_instbench.json).
 
-cpu_baseline: the oracle's STARK prover (C/OpenMP kernels, kind "port") on a
+cpu_baseline (--full): the oracle's STARK prover (C/OpenMP kernels, kind "port") on a
 bounded sample of the same instance shape (2^--cpu-sample-bits rows), rank 0
 at N=1; `full_size` quotes the committed measurement of the oracle at 2^23
 (`bench.py --cpu-full`, profiles/*_cpu_full_stark.json) when one exists.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only what the headline figure needs: setup, warmup, the K
+timed steps, the result line (with the per-kernel and per-stage tables the
+timed steps themselves produce).  Everything that takes runs of its own -- the
+secondary LDE line and its roofline, the trace hand-off, the zkEVM-shaped
+quotient block, the fork-9 / zkEVM-shaped child proofs (sharded_one_proof,
+north_star) and every cpu_baseline -- runs under --full only, where the
+--no-* switches still drop single parts.  At N > 1 the one config-4 proof over
+all ranks is the headline, so that child run belongs to the plain run too.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as
+DIR/<name>.npy (float64): the proof buffer (stark, stark-sharded), or a fixed
+seeded sample of the LDE / Merkle nodes / quotient columns.  The values are
+64-bit field words; each array is stored as two exact float64 arrays, its low
+and high 32-bit halves (<name>_lo32, <name>_hi32).  Inputs are seeded, so two
+runs with the same arguments dump the same arrays.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                   [--workload stark|lde|merkle|stark-sharded|step42ns] [--zkevm-shaped] [--no-cpu] [--no-lde]
 """
 import argparse
@@ -58,6 +74,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the secondary LDE line, the trace hand-off, the "
+                         "zkEVM-shaped quotient, the fork-9 / zkEVM-shaped child proofs and the CPU baselines "
+                         "(the --no-* switches drop single parts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64; 64-bit "
+                         "words as exact low / high 32-bit halves; large outputs as a fixed seeded sample)")
     ap.add_argument("--ncols", type=int, default=100)
     ap.add_argument("--log-n", type=int, default=23)
     ap.add_argument("--blowup-bits", type=int, default=1)
@@ -462,9 +485,38 @@ def kernel_table(kernels):
                 "GB/s": round(v[2] / v[0] / (v[1] / v[0] * 1e-3) / 1e9, 1)} for k, v in kernels.items() if v[0]}
 
 
-def lde_measure(args, dev, torch, world, dist):
+DUMP_SAMPLE = 1 << 20  # words kept of a large output: 2 x 8 MB as float64 halves
+
+
+def sample_dev(t, torch):
+    """The 64-bit words of device tensor `t` as a host uint64 array: all of
+    them up to DUMP_SAMPLE, else the words at DUMP_SAMPLE fixed seeded flat
+    positions (the same positions in every run of the same shape)."""
+    import numpy as np
+    flat = t.reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.random.default_rng(0xD0).integers(0, flat.numel(), DUMP_SAMPLE, dtype=np.int64)
+        flat = flat[torch.from_numpy(idx).to(t.device)]
+    return flat.cpu().numpy().view(np.uint64)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each uint64 array of `arrays` as <name>_lo32.npy and
+    <name>_hi32.npy, float64 (every 32-bit half is exact in a float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.uint64).reshape(-1)
+        if a.size > 2 * DUMP_SAMPLE:
+            a = a[np.random.default_rng(0xD0).integers(0, a.size, DUMP_SAMPLE, dtype=np.int64)]
+        np.save(os.path.join(dirname, name + "_lo32.npy"), (a & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        np.save(os.path.join(dirname, name + "_hi32.npy"), (a >> np.uint64(32)).astype(np.float64))
+
+
+def lde_measure(args, dev, torch, world, dist, dump=None):
     """configs[1]: LDE 2^log_n -> 2^(log_n+blow) x ncols, column-major in HBM.
-    Returns (lde dict, roofline dict)."""
+    Returns (lde dict, roofline dict); dump: a dict that gets a sample of the
+    last step's output as "lde"."""
     import zkgpu
     n = 1 << args.log_n
     ne = n << args.blowup_bits
@@ -502,6 +554,8 @@ def lde_measure(args, dev, torch, world, dist):
                       % (args.log_n, args.log_n + args.blowup_bits, C),
            "ms_per_lde": round(elapsed / steps * 1e3, 4), "device_ms_per_lde": round(dev_ms, 4), "steps": steps,
            "kernels": kernel_table(passes)}
+    if dump is not None:
+        dump["lde"] = sample_dev(out, torch)
     del trace, out
     torch.cuda.empty_cache()
     return lde, roof
@@ -782,6 +836,8 @@ def sharded_children(args, world, rank, local, dist, torch):
     # run at 2^23 fails, it runs again at 2^22 (and says so).
     single = world == 1  # the fork-9 runs through `--workload stark` (one GPU, AUTO plan -> lean)
     runs = [("config4", [], False), ("fork9", ["--fork9"], single), ("fork9_zkevm_shaped", ["--zkevm-shaped"], single)]
+    if not args.full:
+        runs = runs[:1]  # a plain run at N > 1: only the headline's one config-4 proof
     out = {}
     for name, extra, one_gpu in runs:
         ok, rec = _sharded_child(args, world, rank, local, dist, torch, extra, "rccl", one_gpu)
@@ -1017,8 +1073,10 @@ def main():
     lean = False
     sharded = None
     lde = roof = handoff = quotient = None
+    outputs = {} if args.dump_outputs and rank == 0 else None  # --dump-outputs: the last timed step's result
+    last = [None]
     if args.workload == "lde":
-        lde, roof = lde_measure(args, dev, torch, world, dist)
+        lde, roof = lde_measure(args, dev, torch, world, dist, outputs)
         elapsed = lde["ms_per_lde"] * 1e-3 * args.steps
         value, unit, hib = lde["value"], "Gelem/s", True
         kernels = None
@@ -1036,7 +1094,7 @@ def main():
                 prepare = gs.witness
 
             def step():
-                gs.prove_raw()
+                last[0] = gs.prove_raw()
         elif args.workload == "stark-sharded":
             # the C++ row-sharded prover (host/sharded_starks.hpp) over RCCL,
             # or over host shared memory (--comm shm: outboxes sized for the
@@ -1052,7 +1110,7 @@ def main():
             gs.witness()
 
             def step():
-                gs.prove_raw()
+                last[0] = gs.prove_raw()
         elif args.workload == "step42ns":
             step, s42 = step42ns_setup(args, dev, torch, g)
         else:  # merkle
@@ -1072,6 +1130,14 @@ def main():
         else:
             value, unit, hib = n * C * world * args.steps / elapsed / 1e9, "Gelem/s", True
         stages = gs.timers() if gs is not None else None
+        if outputs is not None:
+            if args.workload in ("stark", "stark-sharded"):
+                outputs["proof"] = last[0]
+            elif args.workload == "step42ns":
+                outputs["q_2ns"] = sample_dev(s42["tensors"][10][0], torch)
+            else:
+                outputs["merkle_nodes"] = sample_dev(nodes, torch)
+                outputs["merkle_root"] = sample_dev(nodes[-4:], torch)
         lean = prepare is not None
         if lean:
             # a lean prover holds what the HBM had to spare (its kept columns):
@@ -1080,17 +1146,17 @@ def main():
             gs = prepare = step = None
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
-        if args.workload == "stark" and not args.no_lde:
+        if args.workload == "stark" and args.full and not args.no_lde:
             lde, roof = lde_measure(args, dev, torch, world, dist)
-        if args.workload == "stark" and world == 1 and not args.no_handoff and not lean:
+        if args.workload == "stark" and args.full and world == 1 and not args.no_handoff and not lean:
             handoff = handoff_measure(n, inst.n_cm1, dev, torch, zkgpu, value)
             handoff["pipelined"] = handoff_pipelined(gs, value)
-        if args.workload == "stark" and world == 1 and args.log_n == 23 and not args.no_s42:
+        if args.workload == "stark" and args.full and world == 1 and args.log_n == 23 and not args.no_s42:
             gs = None  # the config-4 instance's HBM back before the 200 GB of fork-9-width sections
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
             quotient = quotient_measure(args, dev, torch, world, dist)
-        if args.workload == "stark" and not args.no_sharded:
+        if args.workload == "stark" and (args.full or world > 1) and not args.no_sharded:
             gs = None  # the replica prover's HBM back for the children
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
@@ -1117,7 +1183,7 @@ def main():
                                 "replica throughput" % world)
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             if args.workload == "stark":
                 cpu = cpu_baseline_stark(min(args.cpu_sample_bits, args.log_n), args.blowup_bits, C, args.queries)
                 full = cpu_full_size_record()
@@ -1250,6 +1316,8 @@ def main():
                 if comm:
                     res["comm"] = comm
         res["cpu_baseline"] = cpu
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -84,3 +84,32 @@ def test_shm_outbox_covers_the_largest_exchange():
     zk = types.SimpleNamespace(n_cm1=751, n_cm2=168, n_cm3=408, n_cm4=6, n_const=234)
     args20 = types.SimpleNamespace(log_n=20, blowup_bits=1)
     assert bench.shm_outbox_bytes(zk, args20, 8) <= 2 << 30 and bench.shm_outbox_bytes(zk, args20, 2) <= 4 << 30
+
+
+def test_dump_outputs_halves_are_exact(tmp_path):
+    """--dump-outputs stores each 64-bit word as two float64 halves: the words
+    come back exactly, and an output above the cap is a fixed seeded sample."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(7)
+    a = rng.integers(0, 2**64 - 1, size=1000, dtype=np.uint64)
+    a[:2] = (0, 2**64 - 1)
+    big = rng.integers(0, 2**64 - 1, size=2 * bench.DUMP_SAMPLE + 1, dtype=np.uint64)
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), {"proof": a, "big": big})
+    lo, hi = np.load(tmp_path / "x" / "proof_lo32.npy"), np.load(tmp_path / "x" / "proof_hi32.npy")
+    assert lo.dtype == hi.dtype == np.float64
+    assert np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), a)
+    bx, by = np.load(tmp_path / "x" / "big_lo32.npy"), np.load(tmp_path / "y" / "big_lo32.npy")
+    assert bx.size == bench.DUMP_SAMPLE and np.array_equal(bx, by)
+    assert sum(f.stat().st_size for f in (tmp_path / "x").iterdir()) <= 64 << 20
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert not args.full and args.dump_outputs is None and args.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "d"

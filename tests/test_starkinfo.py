@@ -151,9 +151,12 @@ def test_zkin_key_order_matches_golden():
 
 @pytest.mark.parametrize("patch,msg", [
     (lambda j: j["varPolMap"][0].update(section="cm9_n"), "string2section() found invalid string=cm9_n"),
-    (lambda j: j["step2prev"]["first"][0]["src"][0].update(type="bogus"), "StepType::setType() found invalid type"),
-    (lambda j: j["step42ns"]["first"][0].update(op="div"), "StepOperation::setOperation() found invalid type"),
-    (lambda j: j["evMap"][0].update(type="tmp"), "EvMap::setType() found invalid type"),
+    # explicit ids: the messages hold "::", which a test id must not (it separates module and test there)
+    pytest.param(lambda j: j["step2prev"]["first"][0]["src"][0].update(type="bogus"),
+                 "StepType::setType() found invalid type", id="bad-step-source-type"),
+    pytest.param(lambda j: j["step42ns"]["first"][0].update(op="div"),
+                 "StepOperation::setOperation() found invalid type", id="bad-step-operation"),
+    pytest.param(lambda j: j["evMap"][0].update(type="tmp"), "EvMap::setType() found invalid type", id="bad-evmap-type"),
     (lambda j: j.pop("mapSectionsN"), "missing key \"mapSectionsN\""),
     (lambda j: j["step3prev"]["first"][0]["src"].append({"type": "tree1", "id": 0}), "takes 2 sources"),
 ])

@@ -7,12 +7,15 @@
 #          zkevm northstar profns sharded
 #   parametrised (replace the round-by-round one-off scripts):
 #     pytest:<file>[,<file>...]   those test files (-x -v, 300 s per test)
-#     benchargs:<tag>             python bench.py $BENCH_ARGS -> gpurun_out/bench_<tag>.json
+#     benchargs:<tag>             python bench.py $BENCH_ARGS (add --full for more than the headline) -> bench_<tag>.json
 #     ab:<tag>                    tools/ab_lib.sh <tag> $AB_ARGS (this tree's lib vs lib_ab)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOTDIR=$(pwd)
 mkdir -p gpurun_out
+# where the bench / benchq / merkle steps write (JOB_OUT: the folder the job's results are collected from)
+OUT=${JOB_OUT:-job_out}
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 ok_or_stop() {
     local rc=$1 what=$2
@@ -42,14 +45,14 @@ for step in "$@"; do
         tail -3 gpurun_out/smoke.log
         ;;
     bench)
-        timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
+        timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
         ok_or_stop $? "bench"
-        cat gpurun_out/bench.json
+        cat "$OUT/bench.json"
         ;;
     benchq)
-        timeout -k 10 600 python bench.py --no-cpu > gpurun_out/benchq.json 2> gpurun_out/benchq.err
+        timeout -k 10 600 python bench.py --full --no-cpu > "$OUT/benchq.json" 2> "$OUT/benchq.err"
         ok_or_stop $? "bench (no cpu)"
-        cat gpurun_out/benchq.json
+        cat "$OUT/benchq.json"
         ;;
     instbench)
         timeout -k 10 120 build/instbench > gpurun_out/instbench.json 2> gpurun_out/instbench.err
@@ -73,7 +76,7 @@ for step in "$@"; do
     prof)
         cd /tmp
         timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$ROOTDIR/gpurun_out/prof" -o run \
-            --output-format csv -- python3 "$ROOTDIR/bench.py" --no-cpu \
+            --output-format csv -- python3 "$ROOTDIR/bench.py" --full --no-cpu \
             > "$ROOTDIR/gpurun_out/prof_bench.json" 2> "$ROOTDIR/gpurun_out/prof.err"
         rc=$?
         cd "$ROOTDIR"
@@ -102,9 +105,9 @@ for step in "$@"; do
         cat gpurun_out/bench_step42ns.json
         ;;
     merkle)
-        timeout -k 10 600 python bench.py --workload merkle --steps 3 --warmup 1 > gpurun_out/bench_merkle.json 2> gpurun_out/bench_merkle.err
+        timeout -k 10 600 python bench.py --full --workload merkle --steps 3 --warmup 1 > "$OUT/bench_merkle.json" 2> "$OUT/bench_merkle.err"
         ok_or_stop $? "bench merkle"
-        cat gpurun_out/bench_merkle.json
+        cat "$OUT/bench_merkle.json"
         ;;
     zkevm)
         timeout -k 10 300 python -u bench.py --workload stark --zkevm-shaped --log-n 22 --steps 3 --warmup 1 --no-cpu \

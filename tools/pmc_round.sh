@@ -2,7 +2,7 @@
 # Counters and kernel statistics bench.py's ratios come from, collected on the
 # GPU box from ONE build of the tree, then summarised and stamped by
 # tools/pmc_summary.py (zkgpu/stamp.py source hashes) into profiles/<tag>_*.
-#   stats    rocprofv3 --kernel-trace --stats of the default bench command
+#   stats    rocprofv3 --kernel-trace --stats of the full bench command (bench.py --full)
 #   stark    one config-4 proof: SQ (+ GRBM clock) / FETCH_SIZE / WRITE_SIZE passes
 #   lde      configs[1] LDE: the same three passes
 #   s42      the zkEVM-shaped quotient (step42ns-shaped program, 2^24 rows): the same
@@ -32,7 +32,7 @@ for step in $STEPS; do
     case $step in
     stats)
         timeout -s KILL 600 rocprofv3 --kernel-trace --stats -d $O/stats -o p --output-format csv -- \
-            python3 $R/bench.py --steps 5 --warmup 2 --no-cpu --no-sharded > $O/stats_bench.json 2> $O/stats.log
+            python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu --no-sharded > $O/stats_bench.json 2> $O/stats.log
         rc=$?; echo "[pmc_round] stats rc=$rc"; [ $rc -eq 0 ] || exit $rc
         ;;
     stark)
