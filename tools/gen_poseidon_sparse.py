@@ -264,7 +264,7 @@ def perm_blocks(st, rc, pre, d0, blocks):
     return st
 
 
-def emit(path, pre, post, D0, W, V, d0tab=None, btabs=None):
+def emit(path, pre, post, D0, W, V, d0tab=None, btabs=None, cap0=None):
     def arr(name, vals, per=4):
         out = [f"static constexpr uint64_t {name}[{len(vals)}] = {{"]
         for i in range(0, len(vals), per):
@@ -303,6 +303,11 @@ def emit(path, pre, post, D0, W, V, d0tab=None, btabs=None):
                   f"#define ZKGPU_PSB_BLOCK_WORDS {len(btabs[0])}"]
         lines += arr32("ZKGPU_PSB_D0", d0tab)
         lines += arr32("ZKGPU_PSB_BLOCKS", [w for t in btabs for w in t])
+    if cap0 is not None:
+        lines += ["// round 0 of a state whose lanes 8..11 enter as zero: their S-box outputs",
+                  "// (0 + RC[8 + k])^7 through the linear layer, plus the round-1 constants:",
+                  "// K[x] = RC[12 + x] + sum_k M[x][8 + k] RC[8 + k]^7"]
+        lines += arr("ZKGPU_PS_CAP0_K", cap0)
     lines += ["#endif  // ZKGPU_POSEIDON_GL_SPARSE_H", ""]
     with open(path, "w") as f:
         f.write("\n".join(lines))
@@ -320,7 +325,19 @@ def main():
     for _ in range(16):
         st = [rnd.randrange(P) for _ in range(12)]
         assert perm_blocks(st, rc, pre, d0tab, btabs) == perm_textbook(st, rc)
-    emit(os.path.join(ROOT, "zkevm-prover_amd/csrc/poseidon_gl_sparse.h"), pre, post, D0, W, V, d0tab, btabs)
+    # a state whose lanes 8..11 are zero (a tree node, a sponge's first block):
+    # their round-0 S-boxes see the round constants alone
+    # alone: a constant vector through the linear layer, folded into the
+    # round-1 constants
+    M = mds()
+    sbox = [pow(rc[8 + k], 7, P) for k in range(4)]
+    cap0 = [(rc[12 + x] + sum(M[x][8 + k] * sbox[k] for k in range(4))) % P for x in range(12)]
+    for _ in range(16):
+        st = [rnd.randrange(P) for _ in range(8)] + [0] * 4
+        r0 = [pow((s + c) % P, 7, P) for s, c in zip(st, rc[:12])]
+        full = [(v + c) % P for v, c in zip(matvec(M, r0), rc[12:24])]
+        assert full == [(v + c) % P for v, c in zip(matvec(M, r0[:8] + [0] * 4), cap0)]
+    emit(os.path.join(ROOT, "zkevm-prover_amd/csrc/poseidon_gl_sparse.h"), pre, post, D0, W, V, d0tab, btabs, cap0)
     print("sparse and block forms verified on random states; header written")
 
 

@@ -92,8 +92,8 @@ __global__ void __launch_bounds__(256) k_perm(uint64_t *st_all, uint64_t n, int 
         if constexpr (V == 5) perm_fast_fold(st);
         if constexpr (V == 6) perm_fast_v1(st);
         if constexpr (V == 7) {  // the 8 full rounds only (timing split)
-            full_rounds_fold(st, 0);
-            full_rounds_fold(st, 26);
+            full_rounds_fold(st, 0, 4);
+            full_rounds_fold(st, 26, 4);
         }
         if constexpr (V == 8) partial_rounds_blocks(st);  // the 22 partial rounds only
     }

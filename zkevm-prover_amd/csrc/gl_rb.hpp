@@ -10,13 +10,20 @@
 namespace zk {
 
 // gl_reduce128 with the rare correction of lo - hh (a borrow needs lo < hh <
-// 2^32: about 2^-32 of products)
+// 2^32: about 2^-32 of products).  The subtraction is a 32-bit
+// subtract-with-borrow chain whose last borrow is the exact condition
+// lo < hh and feeds the ballot directly: a 64-bit __builtin_sub_overflow is
+// narrowed to the same two instructions, but its overflow flag is then
+// re-derived with a 64-bit compare of a re-assembled lo.
 __device__ __forceinline__ uint64_t gl_reduce128_rb(uint64_t lo, uint64_t hi)
 {
     const uint32_t hh = (uint32_t)(hi >> 32);
     const uint32_t hl = (uint32_t)hi;
-    uint64_t t0, r;
-    const bool br = __builtin_sub_overflow(lo, (uint64_t)hh, &t0);
+    uint32_t b0, b1;
+    const uint32_t d0 = __builtin_subc((uint32_t)lo, hh, 0u, &b0);
+    const uint32_t d1 = __builtin_subc((uint32_t)(lo >> 32), 0u, b0, &b1);
+    uint64_t t0 = ((uint64_t)d1 << 32) | d0, r;
+    const bool br = b1 != 0;
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(br) != 0, 0)) t0 -= br ? ZK_EPS : 0ULL;
     const uint64_t t1 = ((uint64_t)hl << 32) - hl;
     const bool c = __builtin_add_overflow(t0, t1, &r);

@@ -19,15 +19,22 @@
 namespace zk {
 
 // ---------------------------------------------------------------- kernels
-__global__ void k_poseidon_batch(uint64_t *out, const uint64_t *in, uint64_t n, int full)
+// FULL: all 12 output lanes; else lanes 0..3 (a kernel each: one copy of the
+// permutation per kernel keeps both at 5 waves per SIMD)
+template <bool FULL>
+__global__ void k_poseidon_batch(uint64_t *out, const uint64_t *in, uint64_t n)
 {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint64_t st[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) st[k] = in[i * 12 + k];
-    poseidon_perm(st);
-    const int w = full ? 12 : 4;
+    if constexpr (FULL)
+        poseidon_perm(st);
+    else
+        poseidon_perm4<false>(st);
+    constexpr int w = FULL ? 12 : 4;
+#pragma unroll
     for (int k = 0; k < w; k++) out[i * w + k] = gl_canon(st[k]);
 }
 
@@ -58,7 +65,10 @@ __device__ __forceinline__ void leaves_cols(uint64_t *digests, const uint64_t *_
             const uint64_t *b = (!SPLIT || c0 < split) ? src + c0 * ld : src2 + (c0 - split) * ld;
 #pragma unroll
             for (int k = 0; k < 8; k++) st[k] = (uint64_t)k < nk ? b[k * ld + i] : 0;
-            poseidon_perm(st);
+            // only the capacity (lanes 0..3) is kept.  (The first block's zero
+            // capacity is not special-cased: a second copy of the permutation
+            // in this loop takes the kernel to 111 VGPRs, 4 waves per SIMD.)
+            poseidon_perm4<false>(st);
         }
     }
     uint64_t *d = digests + 4 * i;
@@ -99,7 +109,7 @@ __global__ void __launch_bounds__(256) k_leaves_rows(uint64_t *digests, const ui
             }
 #pragma unroll
             for (int k = 0; k < 8; k++) st[k] = (uint64_t)k < nk ? row[c0 + k] : 0;
-            poseidon_perm(st);
+            poseidon_perm4<false>(st);
         }
     }
     uint64_t *d = digests + 4 * i;
@@ -264,9 +274,7 @@ __global__ void __launch_bounds__(256) k_merkle_level(uint64_t *dst, const uint6
     uint64_t st[12];
 #pragma unroll
     for (int k = 0; k < 8; k++) st[k] = lvl[8 * i + k];
-#pragma unroll
-    for (int k = 8; k < 12; k++) st[k] = 0;
-    poseidon_perm(st);
+    poseidon_perm4<true>(st);  // zero capacity: lanes 8..11 are constants after round 0
 #pragma unroll
     for (int k = 0; k < 4; k++) dst[4 * i + k] = gl_canon(st[k]);
 }
@@ -305,7 +313,10 @@ int upload_poseidon_constants(Ctx &c)
 int poseidon_batch(uint64_t *out, const uint64_t *in, uint64_t n, int full, hipStream_t s)
 {
     if (!n) return 0;
-    hipLaunchKernelGGL(k_poseidon_batch, dim3(blocks_for(n, 256)), dim3(256), 0, s, out, in, n, full);
+    if (full)
+        hipLaunchKernelGGL(k_poseidon_batch<true>, dim3(blocks_for(n, 256)), dim3(256), 0, s, out, in, n);
+    else
+        hipLaunchKernelGGL(k_poseidon_batch<false>, dim3(blocks_for(n, 256)), dim3(256), 0, s, out, in, n);
     return check_launch("k_poseidon_batch");
 }
 

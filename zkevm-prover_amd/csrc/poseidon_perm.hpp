@@ -30,7 +30,10 @@ namespace zk {
 // a partial-round dot product's final reduction
 __device__ __forceinline__ uint64_t pfin(const Dot3 &d) { return ZKGPU_POSEIDON_RB ? dot3_fin_rb(d) : d.fin(); }
 
-// gl_mul specialised for squaring: 3 partial products instead of 4
+// gl_mul written for squaring: the cross product a0 a1 appears once in the
+// source, but the compiler folds each of its two additions back into a
+// multiply-add, so this compiles to the same four v_mad_u64_u32 as gl_mul
+// (no partial product is saved).
 __device__ __forceinline__ uint64_t gl_sqr3(uint64_t a)
 {
     const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32);
@@ -46,7 +49,7 @@ __device__ __forceinline__ uint64_t gl_sqr3(uint64_t a)
 }
 
 // S-box products with the reduction's rare correction behind a uniform
-// branch (gl_rb.hpp): 3 fewer VALU per product, 4 products per S-box
+// branch (gl_rb.hpp): 4 products per S-box
 __device__ __forceinline__ uint64_t pow7(uint64_t x)
 {
     const uint64_t x2 = gl_sqr3(x);
@@ -250,6 +253,8 @@ __device__ __forceinline__ void perm_sparse(uint64_t st[12])
 // 32x32+64 multiply-adds: its shift-add strength reduction for the entries 2,
 // 8 and 16 needs zero-extended 64-bit operands (one move each).  The 75-bit
 // row sum is recombined with a 32-bit carry chain.  538 -> 438 VALU per MDS.
+// NR < 12: only rows 0..NR-1 are computed (st[NR..11] keep their inputs).
+template <int NR = 12>
 __device__ __forceinline__ void mds_fold(uint64_t st[12], const uint64_t *K)
 {
     uint32_t lo[12], hi[12];
@@ -267,7 +272,7 @@ __device__ __forceinline__ void mds_fold(uint64_t st[12], const uint64_t *K)
     c[12] = 8;  // MDIAG[0]
     asm volatile("" : "+s"(c[12]));
 #pragma unroll
-    for (int x = 0; x < 12; x++) {
+    for (int x = 0; x < NR; x++) {
         uint64_t sl = (uint32_t)K[x], sh = K[x] >> 32;
 #pragma unroll
         for (int y = 0; y < 12; y++) {
@@ -360,10 +365,12 @@ __device__ __forceinline__ void mds_fft_fold(uint64_t st[12], const uint64_t *K)
 
 static constexpr uint64_t ZKGPU_PS_ZERO12[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-__device__ __forceinline__ void full_rounds_fold(uint64_t st[12], int r0)
+// rounds r0 .. r0 + n - 1 (S-boxes, then the linear layer with the next
+// round's constants folded in)
+__device__ __forceinline__ void full_rounds_fold(uint64_t st[12], int r0, int n)
 {
 #pragma unroll 1
-    for (int r = r0; r < r0 + 4; r++) {
+    for (int r = r0; r < r0 + n; r++) {
 #pragma unroll
         for (int s = 0; s < 12; s++) st[s] = pow7(st[s]);
         const uint64_t *K = r == 3 ? ZKGPU_PSP_PRE : (r == 29 ? ZKGPU_PS_ZERO12 : &ZKGPU_POSEIDON_RC[(r + 1) * 12]);
@@ -441,9 +448,45 @@ __device__ __forceinline__ void perm_fast(uint64_t st[12])
 {
 #pragma unroll
     for (int s = 0; s < 12; s++) st[s] = gl_add(st[s], ZKGPU_POSEIDON_RC[s]);
-    full_rounds_fold(st, 0);
+    full_rounds_fold(st, 0, 4);
     partial_rounds_blocks(st);
-    full_rounds_fold(st, 26);
+    full_rounds_fold(st, 26, 4);
+}
+
+// perm_fast for a caller that keeps only lanes 0..3 of the output (the
+// sponge's capacity, a tree node's digest): the last round is peeled out of
+// the rolled loop and its linear layer computes rows 0..3 only, directly as
+// mds_fold does (163 VALU; the 12-output mds_fft_fold is 351).  Lanes 4..11
+// are left undefined.
+// CAP0: lanes 8..11 enter as zero (a tree node, a sponge's first block), so
+// their round-0 S-box inputs are the round constants: the four S-boxes and
+// their share of the linear layer are the constant vector ZKGPU_PS_CAP0_K
+// (with the round-1 constants folded in), and the layer runs on lanes 0..7
+// (st[8..11] are not read).  Lanes 0..3 are perm_fast's, bit for bit after
+// gl_canon.
+template <bool CAP0>
+__device__ __forceinline__ void perm_fast4(uint64_t st[12])
+{
+    if constexpr (CAP0) {
+#pragma unroll
+        for (int s = 0; s < 8; s++) st[s] = pow7(gl_add(st[s], ZKGPU_POSEIDON_RC[s]));
+#pragma unroll
+        for (int s = 8; s < 12; s++) st[s] = 0;
+        if constexpr (ZKGPU_MDS_FFT)
+            mds_fft_fold(st, ZKGPU_PS_CAP0_K);
+        else
+            mds_fold(st, ZKGPU_PS_CAP0_K);
+        full_rounds_fold(st, 1, 3);
+    } else {
+#pragma unroll
+        for (int s = 0; s < 12; s++) st[s] = gl_add(st[s], ZKGPU_POSEIDON_RC[s]);
+        full_rounds_fold(st, 0, 4);
+    }
+    partial_rounds_blocks(st);
+    full_rounds_fold(st, 26, 3);
+#pragma unroll
+    for (int s = 0; s < 12; s++) st[s] = pow7(st[s]);
+    mds_fold<4>(st, ZKGPU_PS_ZERO12);
 }
 
 // perm_fast with the partial-round tables read from memory (D0, BL: copies
@@ -452,9 +495,9 @@ __device__ __forceinline__ void perm_fast_tab(uint64_t st[12], const uint32_t *D
 {
 #pragma unroll
     for (int s = 0; s < 12; s++) st[s] = gl_add(st[s], ZKGPU_POSEIDON_RC[s]);
-    full_rounds_fold(st, 0);
+    full_rounds_fold(st, 0, 4);
     partial_rounds_blocks(st, D0, BL);
-    full_rounds_fold(st, 26);
+    full_rounds_fold(st, 26, 4);
 }
 
 // ---- K independent permutations per thread, step by step interleaved: the
@@ -585,5 +628,11 @@ __device__ __forceinline__ void perm_fast_k(uint64_t (*st)[12])
 
 // the permutation the product kernels use
 __device__ __forceinline__ void poseidon_perm(uint64_t st[12]) { perm_fast(st); }
+// ... and where they keep only lanes 0..3 (CAP0: lanes 8..11 enter as zero)
+template <bool CAP0>
+__device__ __forceinline__ void poseidon_perm4(uint64_t st[12])
+{
+    perm_fast4<CAP0>(st);
+}
 
 }  // namespace zk
