@@ -127,6 +127,18 @@ int zkgpu_gl_merkletree_dev(uint64_t *nodes, const uint64_t *src, uint64_t ld, u
  * reference's merkelize of the whole section (merkleTreeGL.cpp:37-44). */
 int zkgpu_gl_merkletree2_dev(uint64_t *nodes, const uint64_t *src, const uint64_t *src2, uint64_t ld, uint64_t split,
                              uint64_t ncols, uint64_t nrows);
+/* The same tree built while its section arrives in column chunks: the linear
+ * hash's 4-word capacity is carried between calls in the tree's leaf slots
+ * (the first 4*nrows words of nodes), so after the last chunk they hold the
+ * leaf digests and zkgpu_gl_merkle_finish_dev adds the levels above them.
+ * absorb columns [col0, col0+ncols) of a total_cols-wide section into the
+ * leaf sponge held in nodes[0, 4*nrows); src points at column col0.
+ * col0 % 8 == 0; ncols % 8 == 0 unless this is the last chunk.  A section of
+ * total_cols <= 4 (copied, not hashed) comes as one chunk. */
+int zkgpu_gl_merkle_leaves_absorb_dev(uint64_t *nodes, const uint64_t *src, uint64_t ld, uint64_t col0, uint64_t ncols,
+                                      uint64_t total_cols, uint64_t nrows);
+/* the tree levels over finished leaves (merkle_levels) */
+int zkgpu_gl_merkle_finish_dev(uint64_t *nodes, uint64_t nrows);
 /* device-resident, row-major source (FRI trees: friProve.cpp:117-121) */
 int zkgpu_gl_merkletree_rows_dev(uint64_t *nodes, const uint64_t *src, uint64_t ncols, uint64_t nrows);
 /* ---- constant tree (tools/starkpil/bctree) -----------------------------
@@ -150,6 +162,29 @@ int zkgpu_build_const_tree(uint64_t *tree_out, const uint64_t *const_pols, uint6
  * duration of the call (hipHostRegister). */
 int zkgpu_load_rows_dev(uint64_t *cols, uint64_t ld, const uint64_t *rows, uint64_t nrows, uint64_t ncols,
                         uint64_t block_rows, int register_host);
+/* The same load of the column window [col0, col0+wcols) of the ncols-wide
+ * rows, into columns cols + c*ld (c < wcols; the columns outside the window
+ * are not touched): each block's copy is a strided one (host pitch ncols
+ * words).  The whole width is zkgpu_load_rows_dev. */
+int zkgpu_load_rows_window_dev(uint64_t *cols, uint64_t ld, const uint64_t *rows, uint64_t nrows, uint64_t ncols,
+                               uint64_t col0, uint64_t wcols, uint64_t block_rows, int register_host);
+/* Windows of one host buffer (nrows x ncols), queued one after another from
+ * the caller's thread on streams of the loader's own (stage: caller-owned
+ * device buffer, two halves of at least one window row each; register_host
+ * page-locks `rows` from open to close).  zkgpu_load_stream_window returns
+ * with the window's copies and transposes queued and with the library stream
+ * made to wait for them: work queued on it afterwards sees the columns, while
+ * later windows cross PCIe beside it (a pinned or registered source; the
+ * copies of a pageable one block the caller, which stays correct).  The
+ * first window is ordered after everything queued on the library stream at
+ * open.  zkgpu_load_stream_close waits for what was queued and frees the
+ * loader, also after a failed window.  The prover's streamed stage 1
+ * (zkgpu_stark_prove_from_rows) runs on it.  ZKGPU_STREAM_FAIL_BATCH=k
+ * (tests): window k (from 0) fails before anything of it is queued. */
+int zkgpu_load_stream_open(void **loader, const uint64_t *rows, uint64_t nrows, uint64_t ncols, uint64_t *stage,
+                           uint64_t stage_bytes, int register_host);
+int zkgpu_load_stream_window(void *loader, uint64_t *cols, uint64_t ld, uint64_t col0, uint64_t wcols);
+int zkgpu_load_stream_close(void *loader);
 /* The same load in the background: a host thread of the library runs the
  * block loop on streams of its own (stage: caller-owned device buffer of at
  * least zkgpu_load_rows_stage_bytes bytes), so kernels on the library stream

@@ -110,6 +110,23 @@ int zkgpu_stark_set_const(void *handle, const uint64_t *rows);
 int zkgpu_stark_set_publics(void *handle, const uint64_t *publics);
 uint64_t zkgpu_stark_proof_len(void *handle);
 int zkgpu_stark_prove(void *handle, uint64_t *proof_out);
+/* One proof of the executor's host buffer (n rows x n_cm1, row-major): the
+ * trace is loaded in column batches while stage 1 extends and hashes the
+ * batches already on the device.  Same proof as set_cm1(rows) + prove().
+ * Where the reference starts (prover.cpp:94-116,435: genProof on cmPols in
+ * host memory).  Offered under both single-GPU plans -- the lean plan's way
+ * to overlap the upload, where set_cm1_async is refused -- not on a sharded
+ * prover.  register_host = 1 page-locks `rows` for the call; a pinned or
+ * registered source is what overlaps (a pageable one stays correct, its
+ * copies block the calling thread).  Batches are 128 columns, 64 for a trace
+ * narrower than 256 (ZKGPU_STREAM_COLS overrides, tests); stage 1 is reported as one timer,
+ * STARK_STEP_1_STREAM.  Afterwards as after set_cm1 + prove: the trace is
+ * consumed under LEAN, get_cm1 returns `rows` under RESIDENT.  A pending
+ * set_cm1_async load is dropped.  If a load fails mid-stream the call fails
+ * with the loader's message once everything queued has drained, and prove /
+ * get_cm1 are refused until set_cm1 / witness / a successful
+ * prove_from_rows loads a whole trace. */
+int zkgpu_stark_prove_from_rows(void *handle, const uint64_t *rows, int register_host, uint64_t *proof_out);
 int zkgpu_stark_verkey(void *handle, uint64_t out[4]);
 int zkgpu_stark_publics(void *handle, uint64_t *out);
 /* STARK_STEP_* timers of the last prove (starks.cpp:49-403 names):

@@ -21,6 +21,9 @@
 namespace zk {
 
 int upload_poseidon_constants(Ctx &c);
+// poseidon.hip: one chunk of the chunked leaf sponge (k_leaves_absorb)
+int merkle_leaves_absorb(uint64_t *nodes, const uint64_t *src, uint64_t ld, uint64_t col0, uint64_t ncols,
+                         uint64_t total, uint64_t nrows, hipStream_t s);
 
 static Ctx g_ctx;
 static thread_local char g_err[512] = "";
@@ -569,6 +572,36 @@ int zkgpu_gl_merkletree2_dev(uint64_t *nodes, const uint64_t *src, const uint64_
     return merkle_levels(nodes, nrows, g_ctx.stream);
 }
 
+int zkgpu_gl_merkle_leaves_absorb_dev(uint64_t *nodes, const uint64_t *src, uint64_t ld, uint64_t col0, uint64_t ncols,
+                                      uint64_t total_cols, uint64_t nrows)
+{
+    int rc;
+    if ((rc = require_init())) return rc;
+    if (col0 % 8)
+        return set_error(ZKGPU_ERR_ARG, "merkle_leaves_absorb: col0 %llu must be a multiple of 8",
+                         (unsigned long long)col0);
+    if (col0 > total_cols || ncols > total_cols - col0)
+        return set_error(ZKGPU_ERR_ARG, "merkle_leaves_absorb: columns [%llu, +%llu) outside the section's %llu",
+                         (unsigned long long)col0, (unsigned long long)ncols, (unsigned long long)total_cols);
+    if (total_cols <= 4 && ncols != total_cols)
+        return set_error(ZKGPU_ERR_ARG, "merkle_leaves_absorb: a section of %llu <= 4 columns (copied, not hashed) "
+                         "comes as one chunk", (unsigned long long)total_cols);
+    if (col0 + ncols < total_cols && ncols % 8)
+        return set_error(ZKGPU_ERR_ARG, "merkle_leaves_absorb: %llu columns: only the last chunk may not be a "
+                         "multiple of 8", (unsigned long long)ncols);
+    if (!ncols && total_cols) return set_error(ZKGPU_ERR_ARG, "merkle_leaves_absorb: an empty chunk");
+    return merkle_leaves_absorb(nodes, src, ld, col0, ncols, total_cols, nrows, g_ctx.stream);
+}
+
+int zkgpu_gl_merkle_finish_dev(uint64_t *nodes, uint64_t nrows)
+{
+    int rc;
+    if ((rc = require_init())) return rc;
+    if (!nrows) return 0;
+    if (!is_pow2(nrows)) return set_error(ZKGPU_ERR_ARG, "merkle_finish: nrows must be a power of two");
+    return merkle_levels(nodes, nrows, g_ctx.stream);
+}
+
 int zkgpu_gl_merkletree_rows_dev(uint64_t *nodes, const uint64_t *src, uint64_t ncols, uint64_t nrows)
 {
     int rc;
@@ -678,25 +711,41 @@ int zkgpu_build_const_tree(uint64_t *tree_out, const uint64_t *const_pols, uint6
 // stream, its transpose into the columns on stream ts once copied; a half is
 // refilled only after its transpose has read it.  Returns with the work queued
 // (ts, the copy stream), not finished.
-static int load_rows_blocks(uint64_t *cols, uint64_t ld, const uint64_t *rows, uint64_t nrows, uint64_t ncols,
-                            uint64_t block_rows, uint64_t *stage, hipStream_t cs, hipStream_t ts, hipEvent_t copied[2],
-                            hipEvent_t freed[2])
+// The load takes the window [col0, col0 + wcols) of the ncols-wide rows into
+// columns cols + c*ld (c < wcols): a block's copy is then a strided one (host
+// pitch ncols words, wcols words wide), packed in the stage; the whole width
+// stays the one contiguous copy.  `nb` counts the blocks these streams and
+// events have carried (several windows may share them: the streamed loader
+// below), `half_words` is the fixed distance of the stage's halves.
+struct LoadLane {
+    hipStream_t cs = nullptr, ts = nullptr;
+    hipEvent_t copied[2] = {nullptr, nullptr}, freed[2] = {nullptr, nullptr};
+    uint64_t *stage = nullptr;
+    uint64_t half_words = 0, nb = 0;
+};
+
+static int load_rows_blocks(LoadLane &L, uint64_t *cols, uint64_t ld, const uint64_t *rows, uint64_t nrows,
+                            uint64_t ncols, uint64_t col0, uint64_t wcols, uint64_t block_rows)
 {
     int rc = 0;
     const uint64_t nblocks = (nrows + block_rows - 1) / block_rows;
-    for (uint64_t b = 0; b < nblocks && !rc; b++) {
-        const int k = (int)(b & 1);
+    for (uint64_t b = 0; b < nblocks && !rc; b++, L.nb++) {
+        const int k = (int)(L.nb & 1);
         const uint64_t r0 = b * block_rows, nr = std::min(block_rows, nrows - r0);
-        uint64_t *buf = stage + (size_t)k * block_rows * ncols;
-        if (b >= 2 && (rc = check_hip(hipStreamWaitEvent(cs, freed[k], 0), "wait"))) break;
-        if ((rc = check_hip(hipMemcpyAsync(buf, rows + r0 * ncols, nr * ncols * sizeof(uint64_t),
-                                           hipMemcpyHostToDevice, cs),
-                            "H2D")))
-            break;
-        if ((rc = check_hip(hipEventRecord(copied[k], cs), "record"))) break;
-        if ((rc = check_hip(hipStreamWaitEvent(ts, copied[k], 0), "wait"))) break;
-        rows_to_cols(buf, cols + r0, nr, ncols, ld, ts);
-        if ((rc = check_hip(hipEventRecord(freed[k], ts), "record"))) break;
+        uint64_t *buf = L.stage + (size_t)k * L.half_words;
+        const uint64_t *src = rows + r0 * ncols + col0;
+        if (L.nb >= 2 && (rc = check_hip(hipStreamWaitEvent(L.cs, L.freed[k], 0), "wait"))) break;
+        if (wcols == ncols)
+            rc = check_hip(hipMemcpyAsync(buf, src, nr * ncols * sizeof(uint64_t), hipMemcpyHostToDevice, L.cs), "H2D");
+        else
+            rc = check_hip(hipMemcpy2DAsync(buf, wcols * sizeof(uint64_t), src, ncols * sizeof(uint64_t),
+                                            wcols * sizeof(uint64_t), nr, hipMemcpyHostToDevice, L.cs),
+                           "H2D (window)");
+        if (rc) break;
+        if ((rc = check_hip(hipEventRecord(L.copied[k], L.cs), "record"))) break;
+        if ((rc = check_hip(hipStreamWaitEvent(L.ts, L.copied[k], 0), "wait"))) break;
+        rows_to_cols(buf, cols + r0, nr, wcols, ld, L.ts);
+        if ((rc = check_hip(hipEventRecord(L.freed[k], L.ts), "record"))) break;
     }
     return rc;
 }
@@ -707,15 +756,40 @@ static uint64_t load_block_rows(uint64_t block_rows, uint64_t nrows, uint64_t nc
     return std::min(block_rows, nrows);
 }
 
-// one load on its own streams (transposes on ts): the shared body of the
-// synchronous and the background loader
+// the copy stream and the events of a lane whose ts and stage are set
 // `after` (optional): an event both streams wait for before their first
 // command -- the background loader's streams are non-blocking and would
 // otherwise overtake work the caller queued on the library stream into the
 // same buffers (the zeroing memsets of freshly allocated cols / stage).
+static int lane_open(LoadLane &L, hipEvent_t after)
+{
+    int rc = check_hip(hipStreamCreateWithFlags(&L.cs, hipStreamNonBlocking), "copy stream");
+    for (int k = 0; k < 2 && !rc; k++) {
+        rc = check_hip(hipEventCreateWithFlags(&L.copied[k], hipEventDisableTiming), "event");
+        if (!rc) rc = check_hip(hipEventCreateWithFlags(&L.freed[k], hipEventDisableTiming), "event");
+    }
+    if (!rc && after) rc = check_hip(hipStreamWaitEvent(L.cs, after, 0), "wait");
+    if (!rc && after) rc = check_hip(hipStreamWaitEvent(L.ts, after, 0), "wait");
+    return rc;
+}
+// waits for the copy stream, then frees what lane_open made
+static void lane_close(LoadLane &L)
+{
+    if (L.cs) (void)hipStreamSynchronize(L.cs);
+    for (int k = 0; k < 2; k++) {
+        if (L.copied[k]) (void)hipEventDestroy(L.copied[k]);
+        if (L.freed[k]) (void)hipEventDestroy(L.freed[k]);
+        L.copied[k] = L.freed[k] = nullptr;
+    }
+    if (L.cs) (void)hipStreamDestroy(L.cs);
+    L.cs = nullptr;
+}
+
+// one load on its own streams (transposes on ts): the shared body of the
+// synchronous and the background loader
 static int load_rows_streams(uint64_t *cols, uint64_t ld, const uint64_t *rows, uint64_t nrows, uint64_t ncols,
-                             uint64_t block_rows, uint64_t *stage, hipStream_t ts, bool register_host,
-                             hipEvent_t after = nullptr)
+                             uint64_t col0, uint64_t wcols, uint64_t block_rows, uint64_t *stage, hipStream_t ts,
+                             bool register_host, hipEvent_t after = nullptr)
 {
     int rc = 0;
     const size_t total = nrows * ncols * sizeof(uint64_t);
@@ -725,23 +799,14 @@ static int load_rows_streams(uint64_t *cols, uint64_t ld, const uint64_t *rows, 
             return rc;
         registered = true;
     }
-    hipStream_t cs = nullptr;
-    hipEvent_t copied[2] = {nullptr, nullptr}, freed[2] = {nullptr, nullptr};
-    rc = check_hip(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking), "copy stream");
-    for (int k = 0; k < 2 && !rc; k++) {
-        rc = check_hip(hipEventCreateWithFlags(&copied[k], hipEventDisableTiming), "event");
-        if (!rc) rc = check_hip(hipEventCreateWithFlags(&freed[k], hipEventDisableTiming), "event");
-    }
-    if (!rc && after) rc = check_hip(hipStreamWaitEvent(cs, after, 0), "wait");
-    if (!rc && after) rc = check_hip(hipStreamWaitEvent(ts, after, 0), "wait");
-    if (!rc) rc = load_rows_blocks(cols, ld, rows, nrows, ncols, block_rows, stage, cs, ts, copied, freed);
+    LoadLane L;
+    L.ts = ts;
+    L.stage = stage;
+    L.half_words = block_rows * wcols;
+    rc = lane_open(L, after);
+    if (!rc) rc = load_rows_blocks(L, cols, ld, rows, nrows, ncols, col0, wcols, block_rows);
     if (!rc) rc = check_hip(hipStreamSynchronize(ts), "load_rows sync");
-    if (cs) (void)hipStreamSynchronize(cs);
-    for (int k = 0; k < 2; k++) {
-        if (copied[k]) (void)hipEventDestroy(copied[k]);
-        if (freed[k]) (void)hipEventDestroy(freed[k]);
-    }
-    if (cs) (void)hipStreamDestroy(cs);
+    lane_close(L);
     if (registered) (void)hipHostUnregister((void *)rows);
     return rc ? rc : check_launch("rows_to_cols");
 }
@@ -749,14 +814,109 @@ static int load_rows_streams(uint64_t *cols, uint64_t ld, const uint64_t *rows, 
 int zkgpu_load_rows_dev(uint64_t *cols, uint64_t ld, const uint64_t *rows, uint64_t nrows, uint64_t ncols,
                         uint64_t block_rows, int register_host)
 {
+    return zkgpu_load_rows_window_dev(cols, ld, rows, nrows, ncols, 0, ncols, block_rows, register_host);
+}
+
+int zkgpu_load_rows_window_dev(uint64_t *cols, uint64_t ld, const uint64_t *rows, uint64_t nrows, uint64_t ncols,
+                               uint64_t col0, uint64_t wcols, uint64_t block_rows, int register_host)
+{
     int rc;
     if ((rc = require_init())) return rc;
-    if (!nrows || !ncols) return 0;
+    if (col0 > ncols || wcols > ncols - col0)
+        return set_error(ZKGPU_ERR_ARG, "load_rows: window [%llu, +%llu) outside the %llu columns",
+                         (unsigned long long)col0, (unsigned long long)wcols, (unsigned long long)ncols);
+    if (!nrows || !wcols) return 0;
     if (ld < nrows) return set_error(ZKGPU_ERR_ARG, "load_rows: ld %llu < nrows", (unsigned long long)ld);
-    block_rows = load_block_rows(block_rows, nrows, ncols);
-    uint64_t *stage = workspace(2, 2 * block_rows * ncols * sizeof(uint64_t));
+    block_rows = load_block_rows(block_rows, nrows, wcols);
+    uint64_t *stage = workspace(2, 2 * block_rows * wcols * sizeof(uint64_t));
     if (!stage) return ZKGPU_ERR_OOM;
-    return load_rows_streams(cols, ld, rows, nrows, ncols, block_rows, stage, g_ctx.stream, register_host != 0);
+    return load_rows_streams(cols, ld, rows, nrows, ncols, col0, wcols, block_rows, stage, g_ctx.stream,
+                             register_host != 0);
+}
+
+// Streamed loader (zkgpu_load_stream_*): windows of one host buffer queued one
+// after another on a lane that lives across them, from the caller's thread.
+struct LoadStream {
+    LoadLane lane;
+    const uint64_t *rows = nullptr;
+    uint64_t nrows = 0, ncols = 0, windows = 0;
+    long fail_at = -1;  // ZKGPU_STREAM_FAIL_BATCH (tests): window() fails before queuing this one
+    hipEvent_t after = nullptr, done = nullptr;
+    bool registered = false;
+};
+
+int zkgpu_load_stream_open(void **loader, const uint64_t *rows, uint64_t nrows, uint64_t ncols, uint64_t *stage,
+                           uint64_t stage_bytes, int register_host)
+{
+    int rc;
+    *loader = nullptr;
+    if ((rc = require_init())) return rc;
+    if (!rows || !nrows || !ncols || !stage || stage_bytes < 16)
+        return set_error(ZKGPU_ERR_ARG, "load_stream_open: empty buffer or stage");
+    LoadStream *s = new (std::nothrow) LoadStream();
+    if (!s) return set_error(ZKGPU_ERR_OOM, "load_stream_open: loader");
+    s->rows = rows;
+    s->nrows = nrows;
+    s->ncols = ncols;
+    s->lane.stage = stage;
+    s->lane.half_words = stage_bytes / 16;
+    if (const char *e = getenv("ZKGPU_STREAM_FAIL_BATCH")) s->fail_at = strtol(e, nullptr, 10);
+    if (register_host) {
+        rc = check_hip(hipHostRegister((void *)rows, nrows * ncols * sizeof(uint64_t), hipHostRegisterDefault),
+                       "hipHostRegister");
+        s->registered = !rc;
+    }
+    if (!rc) rc = check_hip(hipStreamCreateWithFlags(&s->lane.ts, hipStreamNonBlocking), "loader stream");
+    if (!rc) rc = check_hip(hipEventCreateWithFlags(&s->after, hipEventDisableTiming), "event");
+    if (!rc) rc = check_hip(hipEventCreateWithFlags(&s->done, hipEventDisableTiming), "event");
+    if (!rc) rc = check_hip(hipEventRecord(s->after, g_ctx.stream), "record");
+    if (!rc) rc = lane_open(s->lane, s->after);
+    if (rc) {
+        char msg[sizeof g_err];
+        snprintf(msg, sizeof msg, "%s", g_err);
+        (void)zkgpu_load_stream_close(s);
+        return set_error(rc, "%s", msg);
+    }
+    *loader = s;
+    return 0;
+}
+
+int zkgpu_load_stream_window(void *loader, uint64_t *cols, uint64_t ld, uint64_t col0, uint64_t wcols)
+{
+    LoadStream *s = (LoadStream *)loader;
+    if (!s) return set_error(ZKGPU_ERR_ARG, "load_stream_window: no loader");
+    if (col0 > s->ncols || wcols > s->ncols - col0 || !wcols)
+        return set_error(ZKGPU_ERR_ARG, "load_stream_window: window [%llu, +%llu) outside the %llu columns",
+                         (unsigned long long)col0, (unsigned long long)wcols, (unsigned long long)s->ncols);
+    if (ld < s->nrows) return set_error(ZKGPU_ERR_ARG, "load_stream_window: ld %llu < nrows", (unsigned long long)ld);
+    if (s->lane.half_words < wcols)
+        return set_error(ZKGPU_ERR_ARG, "load_stream_window: a stage half of %llu words holds no row of %llu columns",
+                         (unsigned long long)s->lane.half_words, (unsigned long long)wcols);
+    if ((long)s->windows == s->fail_at)
+        return set_error(ZKGPU_ERR_HIP, "load_stream_window: injected failure before batch %ld (ZKGPU_STREAM_FAIL_BATCH)",
+                         s->fail_at);
+    s->windows++;
+    const uint64_t block_rows = std::min(s->nrows, s->lane.half_words / wcols);
+    int rc = load_rows_blocks(s->lane, cols, ld, s->rows, s->nrows, s->ncols, col0, wcols, block_rows);
+    // recorded before the wait is queued, by this thread: the wait is for this window
+    if (!rc) rc = check_hip(hipEventRecord(s->done, s->lane.ts), "record");
+    if (!rc) rc = check_hip(hipStreamWaitEvent(g_ctx.stream, s->done, 0), "wait");
+    return rc ? rc : check_launch("rows_to_cols");
+}
+
+int zkgpu_load_stream_close(void *loader)
+{
+    LoadStream *s = (LoadStream *)loader;
+    if (!s) return 0;
+    int rc = 0;
+    if (s->lane.ts) rc = check_hip(hipStreamSynchronize(s->lane.ts), "load_stream sync");
+    lane_close(s->lane);
+    if (s->lane.ts) (void)hipStreamDestroy(s->lane.ts);
+    if (s->after) (void)hipEventDestroy(s->after);
+    if (s->done) (void)hipEventDestroy(s->done);
+    if (s->registered) (void)hipHostUnregister((void *)s->rows);
+    delete s;
+    return rc;
 }
 
 // Background loader (zkgpu_load_rows_async): the same block loop in a host
@@ -805,7 +965,7 @@ int zkgpu_load_rows_async(uint64_t *cols, uint64_t ld, const uint64_t *rows, uin
         int r = check_hip(hipSetDevice(device), "hipSetDevice (loader)");
         hipStream_t ts = nullptr;
         if (!r) r = check_hip(hipStreamCreateWithFlags(&ts, hipStreamNonBlocking), "loader stream");
-        if (!r) r = load_rows_streams(cols, ld, rows, nrows, ncols, block_rows, stage, ts, false, t->after);
+        if (!r) r = load_rows_streams(cols, ld, rows, nrows, ncols, 0, ncols, block_rows, stage, ts, false, t->after);
         if (ts) (void)hipStreamDestroy(ts);
         if (r) snprintf(t->err, sizeof t->err, "%s", g_err);
         t->rc = r;

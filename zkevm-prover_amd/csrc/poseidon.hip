@@ -87,6 +87,46 @@ __global__ void __launch_bounds__(256) k_leaves_cols2(uint64_t *digests, const u
     leaves_cols<true>(digests, src, ncols, nrows, ld, src2, split);
 }
 
+// leaves_cols in chunks: columns [col0, col0 + ncols) of a total-wide section
+// (src at column col0), the sponge's capacity carried between launches in the
+// row's leaf slot nodes[4 i .. 4 i + 3] -- as leaves_cols carries it in lanes
+// 0..3 between blocks, non-canonical words included.  col0 and every chunk
+// but the last are multiples of 8, so the blocks are those of the one-launch
+// form; the last chunk zero-pads its tail block and stores the canonical
+// digest.  total <= 4 (copied, not hashed) comes as one chunk.
+__global__ void __launch_bounds__(256) k_leaves_absorb(uint64_t *nodes, const uint64_t *__restrict__ src, uint64_t ld,
+                                                      uint64_t col0, uint64_t ncols, uint64_t total, uint64_t nrows)
+{
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nrows) return;
+    uint64_t st[12];
+    if (total <= 4) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) st[k] = (uint64_t)k < total ? src[k * ld + i] : 0;
+        ncols = 0;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) st[k] = col0 ? nodes[4 * i + k] : 0;
+    }
+#pragma unroll
+    for (int k = 4; k < 12; k++) st[k] = 0;
+    for (uint64_t c0 = 0; c0 < ncols; c0 += 8) {
+        uint64_t nk = ncols - c0 < 8 ? ncols - c0 : 8;
+        // (the section's first block moves the zero capacity: one copy of the
+        // permutation in the loop, as in leaves_cols)
+#pragma unroll
+        for (int k = 0; k < 4; k++) st[8 + k] = st[k];
+        const uint64_t *b = src + c0 * ld;
+#pragma unroll
+        for (int k = 0; k < 8; k++) st[k] = (uint64_t)k < nk ? b[k * ld + i] : 0;
+        poseidon_perm4<false>(st);
+    }
+    const bool last = total > 4 && col0 + ncols == total;
+    uint64_t *d = nodes + 4 * i;
+#pragma unroll
+    for (int k = 0; k < 4; k++) d[k] = last ? gl_canon(st[k]) : st[k];
+}
+
 // leaf digests from a row-major source (row i at src + i*ncols)
 __global__ void __launch_bounds__(256) k_leaves_rows(uint64_t *digests, const uint64_t *__restrict__ src,
                                                     uint64_t ncols, uint64_t nrows)
@@ -333,6 +373,20 @@ int merkle_leaves_cols(uint64_t *digests, const uint64_t *src, uint64_t ncols, u
                            ld);
     prof_end("k_leaves_cols", 8.0 * (double)nrows * (double)ncols + 32.0 * (double)nrows, s);
     return check_launch("k_leaves_cols");
+}
+
+// one chunk of the leaf sponge (arguments checked by the caller); profiled
+// under its own name: "k_leaves_cols" stays the one-launch form's figure
+int merkle_leaves_absorb(uint64_t *nodes, const uint64_t *src, uint64_t ld, uint64_t col0, uint64_t ncols,
+                         uint64_t total, uint64_t nrows, hipStream_t s)
+{
+    if (!nrows) return 0;
+    prof_begin(s);
+    hipLaunchKernelGGL(k_leaves_absorb, dim3(blocks_for(nrows, 256)), dim3(256), 0, s, nodes, src, ld, col0, ncols,
+                       total, nrows);
+    // the chunk's columns, the capacity read (later chunks) and written
+    prof_end("k_leaves_absorb", 8.0 * (double)nrows * (double)ncols + (col0 ? 64.0 : 32.0) * (double)nrows, s);
+    return check_launch("k_leaves_absorb");
 }
 
 int merkle_leaves_rows(uint64_t *digests, const uint64_t *src, uint64_t ncols, uint64_t nrows, hipStream_t s)

@@ -22,7 +22,10 @@
 // step52ns), run as GPU programs (ProverInfo, host/stark_info.cpp); for the
 // zkEVM's parser bytecode, StepsGPU (host/zkgpu_steps.hpp) is the binding.
 //
-// Usage: zkgpu_batch_prover [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]] <config.json>
+// Usage: zkgpu_batch_prover [--stream-trace] [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]]
+//                           <config.json>
+//        (--stream-trace: the trace file's rows stay in host memory and cross
+//        PCIe under stage 1 of the proof, zkgpu_stark_prove_from_rows; single GPU)
 //        (--shard: one rank of ONE proof row-sharded over WORLD processes,
 //        zkgpu_stark_create_sharded; every rank runs this command with the
 //        same config, rank 0 writes the outputs.  rccl: rank 0 writes the
@@ -129,6 +132,7 @@ struct Shard {
     uint32_t rank = 0, world = 1;
     std::string comm;  // "" (single GPU), "rccl:<file>", "host:<name>"
     int device = -1;
+    bool stream_trace = false;  // --stream-trace: zkgpu_stark_prove_from_rows instead of set_cm1 + prove
 };
 
 // The RCCL id through a file: rank 0 writes it (atomic rename), the others
@@ -230,7 +234,8 @@ static int prove(const std::string &config_path, const Shard &sh)
         void *h;
         ~Guard() { zkgpu_stark_destroy(h); }
     } guard{h};
-    if (zkgpu_stark_set_const(h, consts.data()) || zkgpu_stark_set_cm1(h, cm1.data()) ||
+    // (--stream-trace: the trace stays in host memory until the proof loads it under stage 1)
+    if (zkgpu_stark_set_const(h, consts.data()) || (!sh.stream_trace && zkgpu_stark_set_cm1(h, cm1.data())) ||
         zkgpu_stark_set_publics(h, publics.data()))
         throw std::runtime_error(std::string("load: ") + zkgpu_stark_last_error());
     uint64_t verkey[4];
@@ -253,7 +258,8 @@ static int prove(const std::string &config_path, const Shard &sh)
     const uint64_t len = zkgpu_stark_proof_len(h);
     if (len != flat_len(info)) throw std::runtime_error("proof length mismatch");
     std::vector<uint64_t> flat(len);
-    if (zkgpu_stark_prove(h, flat.data())) throw std::runtime_error(std::string("prove: ") + zkgpu_stark_last_error());
+    if (sh.stream_trace ? zkgpu_stark_prove_from_rows(h, cm1.data(), 1, flat.data()) : zkgpu_stark_prove(h, flat.data()))
+        throw std::runtime_error(std::string("prove: ") + zkgpu_stark_last_error());
     const auto t2 = clk::now();
     if (sh.rank == 0) write_outputs(key("outputPath"), flat.data(), len, info, publics);
     const auto t3 = clk::now();
@@ -283,6 +289,11 @@ int main(int argc, char **argv)
         int a = 1;
         while (a + 1 < argc && argv[a][0] == '-' && argv[a][1] == '-') {
             const std::string opt = argv[a];
+            if (opt == "--stream-trace") {
+                sh.stream_trace = true;
+                a += 1;
+                continue;
+            }
             if (opt == "--shard") {
                 unsigned r = 0, w = 0;
                 if (sscanf(argv[a + 1], "%u/%u", &r, &w) != 2 || !w || r >= w)
@@ -300,9 +311,12 @@ int main(int argc, char **argv)
         }
         if (sh.world > 1 && sh.comm.empty())
             throw std::runtime_error("--shard with WORLD > 1 needs --comm");
+        if (sh.stream_trace && !sh.comm.empty())
+            throw std::runtime_error("--stream-trace is for the single-GPU prover (no --comm)");
         if (argc == a + 1 && argv[a][0] != '-') return prove(argv[a], sh);
         fprintf(stderr,
-                "usage: %s [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] <config.json>\n"
+                "usage: %s [--stream-trace] [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] "
+                "<config.json>\n"
                 "       %s --info <starkinfo.json>\n"
                 "       %s --zkin <starkinfo.json> <flat proof> <publics.json> <outdir>\n",
                 argv[0], argv[0], argv[0]);

@@ -726,6 +726,12 @@ public:
         return 0;
     }
     int get_cm1(uint64_t *) override { return fail("stark (sharded): get_cm1 is single-GPU only"); }
+    int prove_from_rows(const uint64_t *, int, uint64_t *) override
+    {
+        return fail("stark (sharded): prove_from_rows is single-GPU only (each rank loads its rows: set_cm1 / "
+                    "set_cm1_async, then prove)");
+    }
+    uint64_t stream_stage_words() const override { return 0; }
 
     // the executor's row-major buffer: the rank takes rows [r0, r0 + ldn) mod N
     int set_cm1(const uint64_t *rows) override

@@ -199,6 +199,14 @@ public:
     void *cm1_ticket[2] = {nullptr, nullptr};
     bool cm1_pending = false;
 
+    // streamed stage 1 (prove_from_rows): the host rows the proof in flight
+    // loads its trace from, the loader's two-half stage, and whether a load
+    // that failed part-way left cm1_n without a whole trace
+    const uint64_t *stream_rows = nullptr;
+    int stream_register = 0;
+    uint64_t *stream_stage = nullptr;
+    bool cm1_broken = false;
+
     virtual ~Starks()
     {
         if (lowered_lde_batch) zkgpu_set_lde_batch_cols(0);
@@ -233,6 +241,14 @@ public:
         return std::max({info.n_cm1, info.n_cm2, info.n_cm3, info.n_const, 1u});
     }
     virtual uint64_t prog_rows_max() const { return NE; }
+    // the streamed stage 1's loader stage: two halves of ~64 MB, as the row
+    // loaders' (a buffer of the prover's own: the library's staging workspace
+    // is shared with the host-pointer calls); 0 where the call is refused
+    virtual uint64_t stream_stage_words() const
+    {
+        const uint64_t b = std::min<uint64_t>(std::max(info.n_cm1, 1u), 128);
+        return 2 * std::min<uint64_t>(N * b, (64ULL << 20) / 8);
+    }
     // at most this many columns per LDE batch (0: the library's default);
     // the sharded prover lowers it when its plan would not fit otherwise
     uint64_t lde_batch_cap = 0;
@@ -249,7 +265,8 @@ public:
         const uint64_t prog_ws = 64ULL * prog_rows_max() * 8;  // <= 64 carried columns between program segments
         const uint64_t h1h2_ws = info.n_pu ? 32ULL * N : 0;    // 2N-slot table + counts + scan
         *bytes = planned + setup_bytes() + std::max(lde_ws, ntt_ws + zkgpu_lde_workspace_bytes(N, NE, 0)) + prog_ws +
-                 h1h2_ws + 24ULL * N;  // + calculateZ scratch
+                 h1h2_ws + 24ULL * N +  // + calculateZ scratch
+                 stream_stage_words() * 8;
         planned = 0;
         return 0;
     }
@@ -620,7 +637,7 @@ public:
         uint64_t ev0[3] = {0, 0, 0};
         if (run(step1, false, ch, ev0, 0)) return -1;
         CK(zkgpu_synchronize());
-        cm1_consumed = false;
+        cm1_consumed = cm1_broken = false;
         return 0;
     }
 
@@ -631,7 +648,7 @@ public:
         if (take_cm1_async(false)) return -1;  // a pending background load is superseded
         if (zkgpu_load_rows_dev(S.sec[SEC_CM1_N], N, rows, N, info.n_cm1, 0, 0))
             return fail("set_cm1: %s", zkgpu_last_error());
-        cm1_consumed = false;
+        cm1_consumed = cm1_broken = false;
         return 0;
     }
 
@@ -639,11 +656,19 @@ public:
     virtual int get_cm1(uint64_t *rows)
     {
         if (lean() && cm1_consumed) return fail("get_cm1: the last proof consumed the trace (lean memory plan)");
+        if (cm1_broken) return fail("get_cm1: the last streamed load failed part-way: no whole trace is loaded");
+        // in row blocks of ~256 MB (no full-size device copy: under the lean
+        // plan a second cm1_n does not fit beside the arena)
         void *tmp = nullptr;
-        const uint64_t bytes = (uint64_t)info.n_cm1 * N * 8;
-        CK(zkgpu_dev_malloc(&tmp, bytes ? bytes : 8));
-        int rc = zkgpu_cols_to_rows_dev((uint64_t *)tmp, S.sec[SEC_CM1_N], N, N, info.n_cm1);
-        if (!rc) rc = zkgpu_memcpy_d2h(rows, tmp, bytes);
+        const uint64_t W1 = info.n_cm1;
+        const uint64_t blk = std::min<uint64_t>(N, std::max<uint64_t>(1, (256ULL << 20) / (std::max<uint64_t>(W1, 1) * 8)));
+        CK(zkgpu_dev_malloc(&tmp, std::max<uint64_t>(8, blk * W1 * 8)));
+        int rc = 0;
+        for (uint64_t r0 = 0; r0 < N && W1 && !rc; r0 += blk) {
+            const uint64_t nr = std::min(blk, N - r0);
+            rc = zkgpu_cols_to_rows_dev((uint64_t *)tmp, S.sec[SEC_CM1_N] + r0, N, nr, W1);
+            if (!rc) rc = zkgpu_memcpy_d2h(rows + r0 * W1, tmp, nr * W1 * 8);
+        }
         zkgpu_dev_free(tmp);
         if (rc) return fail("get_cm1: %s", zkgpu_last_error());
         return 0;
@@ -839,10 +864,101 @@ public:
         return 0;
     }
 
+    // columns per batch of the streamed stage 1, a multiple of 8 (the linear
+    // hash's blocks): 128, the LDE's default column batch, for a wide trace --
+    // the strided block copies move 1 KB per row at 52 GB/s, 256 B per row (32
+    // columns) at 37 GB/s, and the copy is what bounds stage 1 (2^23 rows x
+    // 751 columns: 1.12 s at 128, 1.38 s at 32; extend_pol splits a batch into
+    // its own LDE batches where the plan lowered those) -- and 64 below 256
+    // columns, where a 128-column batch would leave nothing to overlap (2^23
+    // rows x 100 columns: 217 ms at 64, 246 ms in one batch).  Measured by
+    // tools/handoff_stream_ab.py (profiles/r07_handoff_stream.json).
+    // ZKGPU_STREAM_COLS overrides (tests).
+    uint64_t stream_batch_cols() const
+    {
+        uint64_t b = info.n_cm1 >= 256 ? 128 : 64;
+        const char *e = getenv("ZKGPU_STREAM_COLS");
+        if (e && *e) b = strtoull(e, nullptr, 10);
+        return std::max<uint64_t>(8, (b + 7) / 8 * 8);
+    }
+
+    // stage 1 of prove_from_rows: the trace crosses PCIe in column batches,
+    // each into its final place in cm1_n; the library stream waits for a
+    // batch, extends it (resident: into cm1_2ns; lean: into the scratch above
+    // cm1_n up to `split`, into `keep` from there, as commit_cm1_lean) and
+    // absorbs it into tree 1's leaf sponge while the later batches load.
+    // Loads and compute are queued from this one thread: every wait is queued
+    // after the record it waits for.  A failure leaves cm1_broken set.
+    int commit_cm1_stream(Transcript &tr, uint64_t root[4])
+    {
+        const uint64_t W1 = info.n_cm1, split = lean() ? W1 - keep_cols : W1, B = stream_batch_cols();
+        if (lean()) S.sec[SEC_CM1_2NS] = cm1_early;
+        uint64_t *ext_lo = S.sec[SEC_CM1_2NS];
+        if (!stream_stage && dalloc(&stream_stage, stream_stage_words())) return -1;
+        cm1_broken = true;
+        cm1_consumed = false;
+        tstart();
+        void *loader = nullptr;
+        if (zkgpu_load_stream_open(&loader, stream_rows, N, W1, stream_stage, stream_stage_words() * 8,
+                                   stream_register))
+            return fail("prove_from_rows: %s", zkgpu_last_error());
+        int rc = 0;
+        for (uint64_t c0 = 0; c0 < W1 && !rc;) {
+            uint64_t nc = std::min(B, W1 - c0);
+            if (c0 < split && c0 + nc > split) nc = split - c0;  // no batch straddles the two regions
+            uint64_t *cn = S.sec[SEC_CM1_N] + c0 * N;
+            uint64_t *ce = c0 < split ? ext_lo + c0 * NE : keep + (c0 - split) * NE;
+            rc = zkgpu_load_stream_window(loader, cn, N, c0, nc);
+            if (!rc) rc = zkgpu_gl_extend_pol_dev(ce, NE, cn, N, NE, N, nc);
+            if (!rc) rc = zkgpu_gl_merkle_leaves_absorb_dev(nodes[0], ce, NE, c0, nc, W1, NE);
+            c0 += nc;
+        }
+        if (!rc) rc = zkgpu_gl_merkle_finish_dev(nodes[0], NE);
+        if (!rc) rc = zkgpu_memcpy_d2h(root, nodes[0] + zkgpu_gl_merkle_num_elements(NE) - 4, 32);
+        // everything queued is drained before the call returns, failed or not
+        const std::string why = rc ? zkgpu_last_error() : "";
+        const int rc_close = zkgpu_load_stream_close(loader);
+        if (rc) {
+            (void)zkgpu_synchronize();
+            return fail("prove_from_rows: %s", why.c_str());
+        }
+        if (rc_close) return fail("prove_from_rows: %s", zkgpu_last_error());
+        cm1_broken = false;
+        if (tstop("STARK_STEP_1_STREAM")) return -1;
+        tr.put(root, 4);
+        return 0;
+    }
+
+    // STAGE 1 (starks.cpp:49-63)
+    int stage1(Transcript &tr, uint64_t root[4])
+    {
+        if (stream_rows) return commit_cm1_stream(tr, root);
+        if (lean()) return commit_cm1_lean(tr, root);
+        return commit(0, SEC_CM1_N, SEC_CM1_2NS, info.n_cm1, tr, root, "STARK_STEP_1_LDE", "STARK_STEP_1_MERKLETREE");
+    }
+
+    // one proof of the executor's host buffer: set_cm1(rows) + prove() with
+    // the upload under stage 1 (commit_cm1_stream).  A pending background
+    // load is dropped, as by set_cm1.
+    virtual int prove_from_rows(const uint64_t *rows, int register_host, uint64_t *out)
+    {
+        if (!rows || !out) return fail("prove_from_rows: null argument");
+        if (!info.n_cm1) return fail("prove_from_rows: the instance has no committed trace columns");
+        if (take_cm1_async(false)) return -1;
+        stream_rows = rows;
+        stream_register = register_host;
+        const int rc = prove_body(out);
+        stream_rows = nullptr;
+        return rc;
+    }
+
     // the proof of the current cm1_n; a trace queued by set_cm1_async (loaded
     // meanwhile) becomes cm1_n when it returns
     virtual int prove(uint64_t *out)
     {
+        if (cm1_broken)
+            return fail("stark_prove: the last streamed load (prove_from_rows) failed part-way: no whole trace is "
+                        "loaded; load one with set_cm1 or witness first");
         if (lean() && cm1_consumed)
             return fail("stark_prove: the previous proof consumed the trace (lean memory plan: cm1_n is extended in "
                         "place); load the next one with set_cm1 or witness first");
@@ -864,13 +980,7 @@ public:
         uint64_t ch[24] = {0};
         uint64_t roots[4][4];
         std::vector<uint64_t> evals(3 * info.n_ev);
-        // STAGE 1 (starks.cpp:49-63)
-        if (lean()) {
-            if (commit_cm1_lean(tr, roots[0])) return -1;
-        } else if (commit(0, SEC_CM1_N, SEC_CM1_2NS, info.n_cm1, tr, roots[0], "STARK_STEP_1_LDE",
-                          "STARK_STEP_1_MERKLETREE")) {
-            return -1;
-        }
+        if (stage1(tr, roots[0])) return -1;
         // lean: the regions of tmpExp_n / cm2_n / cm3_n held other sections;
         // the columns no stage writes read 0, as under the resident plan
         if (lean() && (zero_unwritten(SEC_TMP_N) || zero_unwritten(SEC_CM2_N) || zero_unwritten(SEC_CM3_N)))
@@ -1255,6 +1365,10 @@ int zkgpu_stark_set_const(void *h, const uint64_t *rows) { return ((Starks *)h)-
 int zkgpu_stark_set_publics(void *h, const uint64_t *publics) { return ((Starks *)h)->set_publics(publics); }
 uint64_t zkgpu_stark_proof_len(void *h) { return ((Starks *)h)->proof_len(); }
 int zkgpu_stark_prove(void *h, uint64_t *out) { return ((Starks *)h)->prove(out); }
+int zkgpu_stark_prove_from_rows(void *h, const uint64_t *rows, int register_host, uint64_t *out)
+{
+    return ((Starks *)h)->prove_from_rows(rows, register_host, out);
+}
 int zkgpu_stark_verkey(void *h, uint64_t out[4])
 {
     memcpy(out, ((Starks *)h)->verkey, 32);

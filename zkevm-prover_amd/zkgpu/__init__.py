@@ -64,6 +64,12 @@ _SIGS = {
     "zkgpu_const_tree_num_elements": (u64, [u64, u32]),
     "zkgpu_build_const_tree": (ctypes.c_int, [vp, vp, u64, u32, u32]),
     "zkgpu_load_rows_dev": (ctypes.c_int, [vp, u64, vp, u64, u64, u64, ctypes.c_int]),
+    "zkgpu_load_rows_window_dev": (ctypes.c_int, [vp, u64, vp, u64, u64, u64, u64, u64, ctypes.c_int]),
+    "zkgpu_load_stream_open": (ctypes.c_int, [ctypes.POINTER(vp), vp, u64, u64, vp, u64, ctypes.c_int]),
+    "zkgpu_load_stream_window": (ctypes.c_int, [vp, vp, u64, u64, u64]),
+    "zkgpu_load_stream_close": (ctypes.c_int, [vp]),
+    "zkgpu_gl_merkle_leaves_absorb_dev": (ctypes.c_int, [vp, vp, u64, u64, u64, u64, u64]),
+    "zkgpu_gl_merkle_finish_dev": (ctypes.c_int, [vp, u64]),
     "zkgpu_load_rows_stage_bytes": (u64, [u64, u64, u64]),
     "zkgpu_load_rows_async": (ctypes.c_int, [vp, u64, vp, u64, u64, u64, vp, u64, ctypes.POINTER(vp)]),
     "zkgpu_load_wait": (ctypes.c_int, [vp]),
@@ -300,6 +306,44 @@ def load_rows_dev(cols, ld, rows, block_rows=0, register_host=False):
                                      int(register_host)), "zkgpu_load_rows_dev")
 
 
+def load_rows_window_dev(cols, ld, rows, col0, wcols, block_rows=0, register_host=False):
+    """columns [col0, col0 + wcols) of host row-major rows -> device columns
+    cols + c*ld, c < wcols (zkgpu_load_rows_window_dev)"""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    nrows, ncols = rows.shape
+    _check(lib().zkgpu_load_rows_window_dev(_addr(cols), ld, rows.ctypes.data, nrows, ncols, col0, wcols, block_rows,
+                                            int(register_host)), "zkgpu_load_rows_window_dev")
+
+
+class RowsStream:
+    """Streamed window loads of one host buffer (zkgpu_load_stream_*):
+    window() queues a column window and makes the library stream wait for
+    it; close() waits for everything queued.  stage: device tensor, two
+    halves of at least one window row each."""
+
+    def __init__(self, rows, stage, register_host=False):
+        self.rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        self.stage = stage
+        nrows, ncols = self.rows.shape
+        self.h = ctypes.c_void_p()
+        _check(lib().zkgpu_load_stream_open(ctypes.byref(self.h), self.rows.ctypes.data, nrows, ncols, _addr(stage),
+                                            stage.numel() * stage.element_size(), int(register_host)),
+               "zkgpu_load_stream_open")
+
+    def window(self, cols, ld, col0, wcols):
+        _check(lib().zkgpu_load_stream_window(self.h, _addr(cols), ld, col0, wcols), "zkgpu_load_stream_window")
+
+    def close(self):
+        h, self.h = self.h, None
+        if h:
+            _check(lib().zkgpu_load_stream_close(h), "zkgpu_load_stream_close")
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h and _lib is not None:
+            _lib.zkgpu_load_stream_close(h)
+
+
 class RowsLoad:
     """Background hand-off (zkgpu_load_rows_async): wait() returns once the
     columns hold the rows.  Keeps the host rows and the staging buffer alive
@@ -376,6 +420,18 @@ def merkletree2_dev(nodes, src, src2, ld, split, ncols, nrows):
     """tree of a section in two regions: columns [0, split) at src, the rest at src2"""
     _check(lib().zkgpu_gl_merkletree2_dev(_addr(nodes), _addr(src), _addr(src2), ld, split, ncols, nrows),
            "zkgpu_gl_merkletree2_dev")
+
+
+def merkle_leaves_absorb_dev(nodes, src, ld, col0, ncols, total_cols, nrows):
+    """one column chunk of a tree's leaf hashes (src at column col0); the
+    sponge state lives in nodes[0, 4*nrows) between the chunks"""
+    _check(lib().zkgpu_gl_merkle_leaves_absorb_dev(_addr(nodes), _addr(src), ld, col0, ncols, total_cols, nrows),
+           "zkgpu_gl_merkle_leaves_absorb_dev")
+
+
+def merkle_finish_dev(nodes, nrows):
+    """the levels above the finished leaves of merkle_leaves_absorb_dev"""
+    _check(lib().zkgpu_gl_merkle_finish_dev(_addr(nodes), nrows), "zkgpu_gl_merkle_finish_dev")
 
 
 def merkletree_rows_dev(nodes, src, ncols, nrows):

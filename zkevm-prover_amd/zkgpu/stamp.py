@@ -26,7 +26,11 @@ FAMILIES = {
 }
 # environment settings that change a family's kernels
 ENV = {
-    "lde": ["ZKGPU_LDE3"],
+    # (the streamed stage 1, zkgpu_stark_prove_from_rows: ZKGPU_STREAM_COLS sets
+    # the columns per load / LDE / leaf-absorb batch, ZKGPU_STREAM_FAIL_BATCH
+    # cuts the stream short -- a profile taken with either set is not the
+    # default path's)
+    "lde": ["ZKGPU_LDE3", "ZKGPU_STREAM_COLS", "ZKGPU_STREAM_FAIL_BATCH"],
     "poseidon": [],
     # the compiler's fusion / term cap change the compiled programs (ZKGPU_ZXP_JIT,
     # interpreter vs compiled, is not one: the profiled workloads pick the

@@ -75,6 +75,7 @@ def slib():
             ("zkgpu_stark_get_cm1", ctypes.c_int, [vp, vp]),
             ("zkgpu_stark_proof_len", u64, [vp]),
             ("zkgpu_stark_prove", ctypes.c_int, [vp, vp]),
+            ("zkgpu_stark_prove_from_rows", ctypes.c_int, [vp, vp, ctypes.c_int, vp]),
             ("zkgpu_stark_verkey", ctypes.c_int, [vp, vp]),
             ("zkgpu_stark_publics", ctypes.c_int, [vp, vp]),
             ("zkgpu_stark_timers", ctypes.c_int, [vp, ctypes.c_char_p, u64, vp, ctypes.c_uint32]),
@@ -355,6 +356,25 @@ class GpuStark:
 
     def prove(self):
         return self.parse(self.prove_raw())
+
+    def prove_from_rows_raw(self, rows, register_host=False):
+        """set_cm1(rows) + prove_raw() with the upload under stage 1
+        (zkgpu_stark_prove_from_rows): rows is the executor's row-major
+        buffer (n x n_cm1) or its host address (a pinned buffer)"""
+        if not isinstance(rows, int):
+            rows = np.ascontiguousarray(rows, np.uint64)
+            if rows.shape != (1 << self.inst.n_bits, self.inst.n_cm1):
+                raise ValueError("rows must be (n, n_cm1) = (%d, %d)" % (1 << self.inst.n_bits, self.inst.n_cm1))
+        n = slib().zkgpu_stark_proof_len(self.h)
+        buf = np.zeros(n, np.uint64)
+        rc = slib().zkgpu_stark_prove_from_rows(self.h, rows if isinstance(rows, int) else rows.ctypes.data,
+                                                int(register_host), buf.ctypes.data)
+        self._cm1_next = None  # a pending background load was waited for and dropped
+        _check(rc, "zkgpu_stark_prove_from_rows")
+        return buf
+
+    def prove_from_rows(self, rows, register_host=False):
+        return self.parse(self.prove_from_rows_raw(rows, register_host))
 
     def timers(self):
         names = ctypes.create_string_buffer(4096)
