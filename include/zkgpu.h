@@ -298,6 +298,14 @@ int zkgpu_copy_rows_dev(uint64_t *dst, uint64_t dst_ld, uint64_t dst_row0, const
                         const uint64_t *src, uint64_t src_ld, uint64_t src_row0, uint32_t src_log_mod,
                         const uint32_t *src_cols, uint32_t ncols, uint64_t nrows);
 
+/* out[j * ncols + c] = src[c * ld + rows[j]] for j < nrows, c < ncols:
+ * rows `rows` (device array, any order, repeats allowed, each < ld) of a
+ * column-major section into a row-major block (the layout
+ * oc_parser_eval_rows / the reference's pols take).  Enqueued on the zkgpu
+ * stream.  A row index >= ld is not read: its block row is zero. */
+int zkgpu_gather_rows_dev(uint64_t *out, const uint64_t *src, uint64_t ld, uint32_t ncols, const uint64_t *rows,
+                          uint64_t nrows);
+
 /* Steps::step*_parser_first (steps.hpp:21-58; used at starks.cpp:73,155,193,
  * 241,371): evaluate one expression program (include/zkgpu_zxp.h) over every
  * row of its domain (2^log_dom rows).  instr/opnd are host arrays (uploaded),

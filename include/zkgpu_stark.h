@@ -135,6 +135,66 @@ int zkgpu_stark_timers(void *handle, char *names_buf, uint64_t names_len, double
 void zkgpu_stark_destroy(void *handle);
 const char *zkgpu_stark_last_error(void);
 
+/* ---- probe: sampled rows around every stage program of a proof ------------
+ * At the full size the sections are tens of GB and live for a fraction of a
+ * second, so the columns the prover computes on the way (tmpExp, cm2, cm3,
+ * q, cm4, f) can only be looked at as a sample of rows taken at the moment
+ * each program runs.  The caller names rows of the n and of the extended
+ * domain; during every later proof the prover records, at each point below,
+ * those rows (plus the rows the point's shifted accesses reach) of every
+ * section the point's program reads (before it runs) and stores to (after),
+ * from the section table in force at that moment, with the challenges and
+ * evaluations in force.  A checker re-evaluates the source program on those
+ * rows (tests/zxp_rows.py); against another prover the first differing record
+ * names the first differing stage.
+ *
+ * Records, in order, per point:
+ *   1 SCALARS record (after = 0, one "row" 0, ncols = 24 + 3 n_ev):
+ *     challenges[24] (those not drawn yet read 0), then evals[3 n_ev] (zero
+ *     before stage 5);
+ *   program points (STEP2, STEP3PREV, STEP3 -- only when the instance has
+ *   that program --, STEP42NS, STEP52NS): after = 0 records of the sections
+ *   the program reads, ascending, then after = 1 records of the sections it
+ *   stores to, ascending.  Rows of a section: the ascending union of
+ *   (r + s) mod dom over the sampled rows r of the program's domain and s in
+ *   {0} + every row shift the program uses with that section (reads and
+ *   stores).  An empty program has the SCALARS record only;
+ *   H1H2 (only with plookups): after = 1, SEC_CM2_N; Z: after = 1, SEC_CM3_N;
+ *   QSPLIT: after = 1, SEC_CM4_2NS -- on the sampled rows of their domain.
+ * Every record covers its section's whole width.  Each record is one
+ * zkgpu_gather_rows_dev on the prover's stream into a device block allocated
+ * by probe_set (outside the memory plan); no host synchronisation is added
+ * inside the proof, one device-to-host copy follows it (timer line
+ * ZKGPU_PROBE_READBACK, after STARK_TOTAL).  A probed proof also zeroes
+ * tmpExp_n / cm2_n / cm3_n after stage 1, so that a column no stage has written
+ * yet reads 0 in a record (not an earlier proof's values, or under the lean
+ * plan the region's former section's).  With no probe set a proof launches
+ * exactly what it launched before. */
+enum { ZKGPU_PROBE_STEP2 = 0, ZKGPU_PROBE_H1H2, ZKGPU_PROBE_STEP3PREV, ZKGPU_PROBE_Z, ZKGPU_PROBE_STEP3,
+       ZKGPU_PROBE_STEP42NS, ZKGPU_PROBE_QSPLIT, ZKGPU_PROBE_STEP52NS, ZKGPU_PROBE_POINTS };
+#define ZKGPU_PROBE_SCALARS 0xFFFFFFFFu   /* record "section": challenges[24] then evals[3 * n_ev] */
+#define ZKGPU_PROBE_MAX_ROWS 4096u
+
+typedef struct {
+    uint32_t point;    /* ZKGPU_PROBE_* */
+    uint32_t after;    /* 0: taken before the point ran, 1: after */
+    uint32_t section;  /* SEC_* or ZKGPU_PROBE_SCALARS */
+    uint32_t ncols;    /* the section's whole width */
+    uint64_t n_rows;
+    uint64_t rows_off; /* into the u64 payload: n_rows row indices, strictly ascending */
+    uint64_t vals_off; /* into the u64 payload: n_rows x ncols, row-major */
+} zkgpu_probe_rec;
+
+/* rows_n / rows_ext: sampled rows of the n and the extended domain (each <= ZKGPU_PROBE_MAX_ROWS,
+ * in range, repeats folded); both empty: probe off.  Holds for every later proof until changed.
+ * Refused: a sharded prover, a row out of range, too many rows, a program that reads or writes
+ * a section of the other domain than its own.  A refusal or a failed allocation leaves the probe off. */
+int zkgpu_stark_probe_set(void *handle, const uint64_t *rows_n, uint32_t n_rows_n,
+                          const uint64_t *rows_ext, uint32_t n_rows_ext);
+/* record count and payload length (u64) of the last successful proof's probe; 0/0 when there is none */
+int zkgpu_stark_probe_size(void *handle, uint32_t *n_recs, uint64_t *n_words);
+int zkgpu_stark_probe_read(void *handle, zkgpu_probe_rec *recs, uint32_t max_recs, uint64_t *payload, uint64_t max_words);
+
 /* ---- the Fiat-Shamir transcript the prover runs on the host, as the
  * reference's class Transcript (transcript.hpp:14-37, transcript.cpp:4-88):
  * Poseidon-GL sponge, 8-element rate, 4-element capacity.  Host code only

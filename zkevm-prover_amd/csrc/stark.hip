@@ -110,6 +110,22 @@ __global__ void k_copy_rows(uint64_t *dst, uint64_t dld, uint64_t drow0, const u
     dst[dc * dld + drow0 + j] = src[sc * sld + ((srow0 + j) & smask)];
 }
 
+// scattered rows of a column-major section into a row-major block (the
+// prover's probe): out[j * ncols + c] = src[c * ld + rows[j]].  Consecutive
+// lanes take consecutive columns of one row: every load is its own cache line
+// whichever way the lanes run (columns are ld * 8 bytes apart, the rows are
+// scattered), the stores are contiguous.  64-bit indices throughout (c * ld
+// passes 2^32 at the zkEVM's widths).  A row index >= ld is not read.
+__global__ void k_gather_rows(uint64_t *out, const uint64_t *src, uint64_t ld, uint32_t ncols, const uint64_t *rows,
+                              uint64_t total)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += stride) {
+        const uint64_t j = k / ncols, c = k - j * ncols, r = rows[j];
+        out[k] = r < ld ? src[c * ld + r] : 0;
+    }
+}
+
 // ---------------------------------------------------------------- ZXP interpreter
 struct ZxpEnv {
     const ZOp *prog;
@@ -670,6 +686,20 @@ int copy_rows(uint64_t *dst, uint64_t dld, uint64_t drow0, const uint32_t *dcols
     return check_launch("k_copy_rows");
 }
 
+static int gather_rows(uint64_t *out, const uint64_t *src, uint64_t ld, uint32_t ncols, const uint64_t *rows, uint64_t nrows,
+                hipStream_t s)
+{
+    if (!ncols || !nrows) return 0;
+    const uint64_t total = nrows * ncols;
+    // grid-stride: at most 2^16 blocks whatever the block's size
+    const uint64_t want = (total + 255) / 256;
+    const uint32_t blocks = want < (1u << 16) ? (uint32_t)want : 1u << 16;
+    prof_begin(s);
+    hipLaunchKernelGGL(k_gather_rows, dim3(blocks), dim3(256), 0, s, out, src, ld, ncols, rows, total);
+    prof_end("k_gather_rows", 16.0 * (double)total + 8.0 * (double)nrows, s);
+    return check_launch("k_gather_rows");
+}
+
 int zxp_eval(const ZxpLaunch &L, hipStream_t s)
 {
     Ctx &c = ctx();
@@ -821,3 +851,14 @@ int cols3_to_interleaved(uint64_t *out, const uint64_t *cols, uint64_t ld, uint6
 }
 
 }  // namespace zk
+
+// the C-ABI of the gather (include/zkgpu.h), beside its kernel
+extern "C" int zkgpu_gather_rows_dev(uint64_t *out, const uint64_t *src, uint64_t ld, uint32_t ncols,
+                                     const uint64_t *rows, uint64_t nrows)
+{
+    if (!zk::ctx().ready) return zk::set_error(ZKGPU_ERR_INIT, "zkgpu_init() not called");
+    if (!ncols || !nrows) return 0;
+    if (!out || !src || !rows) return zk::set_error(ZKGPU_ERR_ARG, "gather_rows: null pointer");
+    if (nrows > UINT64_MAX / ncols) return zk::set_error(ZKGPU_ERR_ARG, "gather_rows: nrows x ncols overflows");
+    return zk::gather_rows(out, src, ld, ncols, rows, nrows, zk::ctx().stream);
+}

@@ -726,6 +726,10 @@ public:
         return 0;
     }
     int get_cm1(uint64_t *) override { return fail("stark (sharded): get_cm1 is single-GPU only"); }
+    int probe_set(const uint64_t *, uint32_t, const uint64_t *, uint32_t) override
+    {
+        return fail("stark (sharded): probe_set is single-GPU only (the sampled rows live on other ranks)");
+    }
     int prove_from_rows(const uint64_t *, int, uint64_t *) override
     {
         return fail("stark (sharded): prove_from_rows is single-GPU only (each rank loads its rows: set_cm1 / "

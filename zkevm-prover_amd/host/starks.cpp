@@ -211,6 +211,7 @@ public:
     {
         if (lowered_lde_batch) zkgpu_set_lde_batch_cols(0);
         for (void *t : cm1_ticket) (void)zkgpu_load_wait(t);
+        probe_clear();
         for (void *p : allocs) zkgpu_dev_free(p);
     }
 
@@ -967,8 +968,227 @@ public:
         return rc ? rc : rc2;
     }
 
+    // ---- probe (include/zkgpu_stark.h): sampled rows of the sections around
+    // every stage program.  probe_set derives the record list from the
+    // programs and allocates the device block the records are gathered into;
+    // prove_body's hooks (probe_point) enqueue one gather per record on the
+    // prover's stream, from the section table as it stands at that moment, and
+    // copy the host scalars; probe_readback brings the block to the host after
+    // the proof.  Nothing here synchronises inside a proof.
+    struct ProbeRec {
+        zkgpu_probe_rec r;
+        uint64_t rows_dev = 0;  // its row list in probe_rows (device), in words
+        uint64_t stage = 0;     // its values in probe_stage (device), in words
+    };
+    std::vector<ProbeRec> probe_recs;
+    std::vector<uint32_t> probe_at[ZKGPU_PROBE_POINTS][2];  // records of (point, after)
+    std::vector<uint64_t> probe_payload;  // row lists and scalars, then the image of probe_stage
+    uint64_t probe_gather0 = 0, probe_stage_words = 0;
+    uint64_t *probe_stage = nullptr, *probe_rows = nullptr;
+    bool probe_valid = false;
+
+    void probe_clear()
+    {
+        if (probe_stage) (void)zkgpu_dev_free(probe_stage);
+        if (probe_rows) (void)zkgpu_dev_free(probe_rows);
+        probe_stage = probe_rows = nullptr;
+        probe_recs.clear();
+        for (auto &pt : probe_at)
+            for (auto &v : pt) v.clear();
+        probe_payload.clear();
+        probe_gather0 = probe_stage_words = 0;
+        probe_valid = false;
+    }
+
+    virtual int probe_set(const uint64_t *rows_n, uint32_t n_rows_n, const uint64_t *rows_ext, uint32_t n_rows_ext)
+    {
+        probe_clear();
+        if (!n_rows_n && !n_rows_ext) return 0;
+        if ((n_rows_n && !rows_n) || (n_rows_ext && !rows_ext)) return fail("probe_set: null row list");
+        if (n_rows_n > ZKGPU_PROBE_MAX_ROWS || n_rows_ext > ZKGPU_PROBE_MAX_ROWS)
+            return fail("probe_set: %u / %u sampled rows, at most %u per domain", n_rows_n, n_rows_ext,
+                        ZKGPU_PROBE_MAX_ROWS);
+        std::vector<uint64_t> base[2] = {std::vector<uint64_t>(rows_n, rows_n + n_rows_n),
+                                         std::vector<uint64_t>(rows_ext, rows_ext + n_rows_ext)};
+        for (int e = 0; e < 2; e++) {
+            std::sort(base[e].begin(), base[e].end());
+            base[e].erase(std::unique(base[e].begin(), base[e].end()), base[e].end());
+            const uint64_t dom = e ? NE : N;
+            if (!base[e].empty() && base[e].back() >= dom)
+                return fail("probe_set: row %llu is outside the %s domain (%llu rows)",
+                            (unsigned long long)base[e].back(), e ? "extended" : "n", (unsigned long long)dom);
+        }
+        std::vector<std::vector<uint64_t>> lists;  // row list of each record
+        auto add = [&](uint32_t point, uint32_t after, uint32_t sec, uint32_t ncols, std::vector<uint64_t> rows) {
+            ProbeRec p;
+            p.r = {point, after, sec, ncols, (uint64_t)rows.size(), 0, 0};
+            probe_at[point][after].push_back((uint32_t)probe_recs.size());
+            probe_recs.push_back(p);
+            lists.push_back(std::move(rows));
+        };
+        const uint32_t n_scal = 24 + 3 * info.n_ev;
+        struct Point {
+            uint32_t point;
+            const Prog *prog;  // null: a stage step with one after-record
+            bool ext, present;
+            uint32_t sec;
+            const char *name;
+        };
+        const Point points[ZKGPU_PROBE_POINTS] = {
+            {ZKGPU_PROBE_STEP2, &step2, false, true, 0, "step2"},
+            {ZKGPU_PROBE_H1H2, nullptr, false, info.n_pu != 0, SEC_CM2_N, "h1h2"},
+            {ZKGPU_PROBE_STEP3PREV, &step3prev, false, true, 0, "step3prev"},
+            {ZKGPU_PROBE_Z, nullptr, false, true, SEC_CM3_N, "z"},
+            {ZKGPU_PROBE_STEP3, &step3, false, !step3.instr.empty(), 0, "step3"},
+            {ZKGPU_PROBE_STEP42NS, &step42ns, true, true, 0, "step42ns"},
+            {ZKGPU_PROBE_QSPLIT, nullptr, true, true, SEC_CM4_2NS, "qsplit"},
+            {ZKGPU_PROBE_STEP52NS, &step52ns, true, true, 0, "step52ns"},
+        };
+        for (const Point &pt : points) {
+            if (!pt.present) continue;
+            add(pt.point, 0, ZKGPU_PROBE_SCALARS, n_scal, {0});
+            const uint64_t dom = pt.ext ? NE : N;
+            if (!pt.prog) {
+                add(pt.point, 1, pt.sec, S.ncols[pt.sec], base[pt.ext]);
+                continue;
+            }
+            // the sections the program reads / stores to, and every row shift it uses with each
+            std::vector<int32_t> shifts[SEC_COUNT];
+            bool reads[SEC_COUNT] = {false}, stores[SEC_COUNT] = {false};
+            auto use = [&](uint32_t k, bool store) -> int {
+                if (k >= pt.prog->opnd.size()) return fail("probe_set: %s names operand %u of %zu", pt.name, k,
+                                                           pt.prog->opnd.size());
+                const zxp_operand &o = pt.prog->opnd[k];
+                if (o.kind != ZXP_COL && o.kind != ZXP_COL3) return 0;
+                if (o.a >= SEC_COUNT) return fail("probe_set: %s names section %u", pt.name, o.a);
+                if ((o.a >= SEC_CM1_2NS) != pt.ext)
+                    return fail("probe_set: %s %s section %u of the other domain: its rows are not the sampled rows'",
+                                pt.name, store ? "writes" : "reads", o.a);
+                (store ? stores : reads)[o.a] = true;
+                shifts[o.a].push_back((int32_t)o.c);
+                return 0;
+            };
+            for (const zxp_instr &in : pt.prog->instr)
+                if (use(in.a, false) || (in.op != ZXP_COPY && use(in.b, false)) || use(in.dst, true)) {
+                    probe_clear();
+                    return -1;
+                }
+            std::vector<uint64_t> rows[SEC_COUNT];
+            for (uint32_t s = 0; s < SEC_COUNT; s++) {
+                if (!reads[s] && !stores[s]) continue;
+                shifts[s].push_back(0);
+                for (uint64_t r : base[pt.ext])
+                    for (int32_t sh : shifts[s]) rows[s].push_back((r + (uint64_t)(int64_t)sh) & (dom - 1));
+                std::sort(rows[s].begin(), rows[s].end());
+                rows[s].erase(std::unique(rows[s].begin(), rows[s].end()), rows[s].end());
+            }
+            for (uint32_t after = 0; after < 2; after++)
+                for (uint32_t s = 0; s < SEC_COUNT; s++)
+                    if (after ? stores[s] : reads[s]) add(pt.point, after, s, S.ncols[s], rows[s]);
+        }
+        // payload: every record's row list (and the scalars' values), then the gathered values
+        uint64_t cur = 0;
+        for (size_t i = 0; i < probe_recs.size(); i++) {
+            zkgpu_probe_rec &r = probe_recs[i].r;
+            r.rows_off = cur;
+            cur += r.n_rows;
+            if (r.section == ZKGPU_PROBE_SCALARS) {
+                r.vals_off = cur;
+                cur += r.ncols;
+            }
+        }
+        probe_gather0 = cur;
+        std::map<std::vector<uint64_t>, uint64_t> seen;  // identical row lists share one device copy
+        std::vector<uint64_t> dev_rows;
+        for (size_t i = 0; i < probe_recs.size(); i++) {
+            ProbeRec &p = probe_recs[i];
+            if (p.r.section == ZKGPU_PROBE_SCALARS) continue;
+            p.stage = probe_stage_words;
+            p.r.vals_off = probe_gather0 + probe_stage_words;
+            probe_stage_words += p.r.n_rows * p.r.ncols;
+            auto it = seen.find(lists[i]);
+            if (it == seen.end()) {
+                it = seen.emplace(lists[i], (uint64_t)dev_rows.size()).first;
+                dev_rows.insert(dev_rows.end(), lists[i].begin(), lists[i].end());
+            }
+            p.rows_dev = it->second;
+        }
+        probe_payload.assign(probe_gather0 + probe_stage_words, 0);
+        for (size_t i = 0; i < probe_recs.size(); i++)
+            std::copy(lists[i].begin(), lists[i].end(), probe_payload.begin() + probe_recs[i].r.rows_off);
+        void *stage = nullptr, *rows = nullptr;
+        if (zkgpu_dev_malloc(&stage, probe_stage_words * 8) || zkgpu_dev_malloc(&rows, dev_rows.size() * 8)) {
+            if (stage) (void)zkgpu_dev_free(stage);
+            const double mb = (double)(probe_stage_words + dev_rows.size()) * 8 / 1e6;
+            probe_clear();
+            return fail("probe_set: the probe's device block (%.1f MB) could not be allocated: %s; the probe is off",
+                        mb, zkgpu_last_error());
+        }
+        probe_stage = (uint64_t *)stage;
+        probe_rows = (uint64_t *)rows;
+        if (zkgpu_memcpy_h2d(probe_rows, dev_rows.data(), dev_rows.size() * 8)) {
+            probe_clear();
+            return fail("probe_set: %s; the probe is off", zkgpu_last_error());
+        }
+        return 0;
+    }
+
+    // the records of (point, after): the scalars from the host, every section from the live table
+    int probe_point(uint32_t point, uint32_t after, const uint64_t ch[24], const std::vector<uint64_t> &evals)
+    {
+        if (probe_recs.empty()) return 0;
+        for (uint32_t i : probe_at[point][after]) {
+            const ProbeRec &p = probe_recs[i];
+            if (p.r.section == ZKGPU_PROBE_SCALARS) {
+                memcpy(&probe_payload[p.r.vals_off], ch, 24 * 8);
+                if (!evals.empty()) memcpy(&probe_payload[p.r.vals_off + 24], evals.data(), evals.size() * 8);
+                continue;
+            }
+            CK(zkgpu_gather_rows_dev(probe_stage + p.stage, S.sec[p.r.section], S.ld[p.r.section], p.r.ncols,
+                                     probe_rows + p.rows_dev, p.r.n_rows));
+        }
+        return 0;
+    }
+    int probed_run(uint32_t point, const Prog &p, bool ext, const uint64_t ch[24], const std::vector<uint64_t> &evals,
+                   uint32_t n_ev)
+    {
+        if (probe_point(point, 0, ch, evals) || run(p, ext, ch, evals.data(), n_ev)) return -1;
+        return probe_point(point, 1, ch, evals);
+    }
+    // after the proof's last kernel and its total timer: the one copy to the host
+    int probe_readback()
+    {
+        if (probe_recs.empty()) return 0;
+        const auto t = clk::now();
+        CK(zkgpu_memcpy_d2h(probe_payload.data() + probe_gather0, probe_stage, probe_stage_words * 8));
+        timers.emplace_back("ZKGPU_PROBE_READBACK", std::chrono::duration<double, std::milli>(clk::now() - t).count());
+        probe_valid = true;
+        return 0;
+    }
+    int probe_size(uint32_t *n_recs, uint64_t *n_words) const
+    {
+        if (n_recs) *n_recs = probe_valid ? (uint32_t)probe_recs.size() : 0;
+        if (n_words) *n_words = probe_valid ? probe_payload.size() : 0;
+        return 0;
+    }
+    int probe_read(zkgpu_probe_rec *recs, uint32_t max_recs, uint64_t *payload, uint64_t max_words) const
+    {
+        if (!probe_valid)
+            return fail("probe_read: no probe to read: none was set (probe_set) before the last proof, or that proof "
+                        "failed");
+        if (!recs || !payload) return fail("probe_read: null buffer");
+        if (max_recs < probe_recs.size() || max_words < probe_payload.size())
+            return fail("probe_read: buffers of %u records / %llu words are too small for %zu records / %zu words "
+                        "(probe_size)", max_recs, (unsigned long long)max_words, probe_recs.size(),
+                        probe_payload.size());
+        for (size_t i = 0; i < probe_recs.size(); i++) recs[i] = probe_recs[i].r;
+        memcpy(payload, probe_payload.data(), probe_payload.size() * 8);
+        return 0;
+    }
+
     int prove_body(uint64_t *out)
     {
+        probe_valid = false;
         timers.clear();
         pend_t.clear();
         pend_x.clear();
@@ -985,15 +1205,24 @@ public:
         // the columns no stage writes read 0, as under the resident plan
         if (lean() && (zero_unwritten(SEC_TMP_N) || zero_unwritten(SEC_CM2_N) || zero_unwritten(SEC_CM3_N)))
             return -1;
+        // probed: a column no stage of this proof has written yet reads 0 in a
+        // record, as in a fresh prover (and the CPU provers' zeroed memory),
+        // not the last proof's values or, lean, those of the region's former
+        // section (the regions are dead here, as for zero_unwritten)
+        if (!probe_recs.empty())
+            for (uint32_t s : {SEC_TMP_N, SEC_CM2_N, SEC_CM3_N})
+                CK(zkgpu_memset_dev(S.sec[s], 0, (uint64_t)S.ncols[s] * N * 8));
         // STAGE 2 (:65-144)
         tr.get_field(ch + 0);
         tr.get_field(ch + 3);
         tstart();
-        if (run(step2, false, ch, evals.data(), 0)) return -1;
+        if (probed_run(ZKGPU_PROBE_STEP2, step2, false, ch, evals, 0)) return -1;
         if (tstop("STARK_STEP_2_CALCULATE_EXPS")) return -1;
         if (info.n_pu) {
             tstart();
-            if (h1h2_all()) return -1;
+            if (probe_point(ZKGPU_PROBE_H1H2, 0, ch, evals) || h1h2_all() ||
+                probe_point(ZKGPU_PROBE_H1H2, 1, ch, evals))
+                return -1;
             if (tstop("STARK_STEP_2_CALCULATEH1H2")) return -1;
         }
         if (commit(1, SEC_CM2_N, SEC_CM2_2NS, info.n_cm2, tr, roots[1], "STARK_STEP_2_LDE", "STARK_STEP_2_MERKLETREE"))
@@ -1002,15 +1231,15 @@ public:
         tr.get_field(ch + 6);
         tr.get_field(ch + 9);
         tstart();
-        if (run(step3prev, false, ch, evals.data(), 0)) return -1;
+        if (probed_run(ZKGPU_PROBE_STEP3PREV, step3prev, false, ch, evals, 0)) return -1;
         if (tstop("STARK_STEP_3_CALCULATE_EXPS")) return -1;
         tstart();
-        if (z_all()) return -1;
+        if (probe_point(ZKGPU_PROBE_Z, 0, ch, evals) || z_all() || probe_point(ZKGPU_PROBE_Z, 1, ch, evals)) return -1;
         if (tstop("STARK_STEP_3_CALCULATE_Z")) return -1;
         // step3: post-Z expressions (starks.cpp:193-208)
         if (!step3.instr.empty()) {
             tstart();
-            if (run(step3, false, ch, evals.data(), 0)) return -1;
+            if (probed_run(ZKGPU_PROBE_STEP3, step3, false, ch, evals, 0)) return -1;
             if (tstop("STARK_STEP_3_CALCULATE_EXPS_2")) return -1;
         }
         if (commit(2, SEC_CM3_N, SEC_CM3_2NS, info.n_cm3, tr, roots[2], "STARK_STEP_3_LDE", "STARK_STEP_3_MERKLETREE"))
@@ -1029,10 +1258,12 @@ public:
             if (tstop("STARK_STEP_4_CM1_LDE")) return -1;
         }
         tstart();
-        if (run(step42ns, true, ch, evals.data(), 0)) return -1;
+        if (probed_run(ZKGPU_PROBE_STEP42NS, step42ns, true, ch, evals, 0)) return -1;
         if (tstop("STARK_STEP_4_CALCULATE_EXPS_2NS")) return -1;
         tstart();
-        if (quotient_pieces(S.sec[SEC_Q_2NS], S.sec[SEC_CM4_2NS])) return -1;
+        if (probe_point(ZKGPU_PROBE_QSPLIT, 0, ch, evals) || quotient_pieces(S.sec[SEC_Q_2NS], S.sec[SEC_CM4_2NS]) ||
+            probe_point(ZKGPU_PROBE_QSPLIT, 1, ch, evals))
+            return -1;
         if (tstop("STARK_STEP_4_CALCULATE_EXPS_2NS_INTT_NTT")) return -1;
         tstart();
         CK(zkgpu_gl_merkletree_dev(nodes[3], S.sec[SEC_CM4_2NS], NE, info.n_cm4, NE));
@@ -1069,10 +1300,11 @@ public:
         CK(zkgpu_xdivxsub_dev(xdiv, xdivw, xi, info.n_bits, info.n_bits_ext));
         if (tstop("STARK_STEP_5_XDIVXSUB")) return -1;
         tstart();
-        if (run(step52ns, true, ch, evals.data(), info.n_ev)) return -1;
+        if (probed_run(ZKGPU_PROBE_STEP52NS, step52ns, true, ch, evals, info.n_ev)) return -1;
         CK(zkgpu_cols3_to_interleaved_dev(fri_pol[0], S.sec[SEC_F_2NS], NE, NE));
         if (tstop("STARK_STEP_5_CALCULATE_EXPS")) return -1;
-        return fri_and_queries(tr, &roots[0][0], evals, out, tall);
+        if (fri_and_queries(tr, &roots[0][0], evals, out, tall)) return -1;
+        return probe_readback();
     }
 
     // calculateH1H2 of every plookup (starks.cpp:104-127), n domain
@@ -1398,6 +1630,20 @@ int zkgpu_stark_timers(void *h, char *names_buf, uint64_t names_len, double *ms,
     return (int)n;
 }
 void zkgpu_stark_destroy(void *h) { delete (Starks *)h; }
+
+int zkgpu_stark_probe_set(void *h, const uint64_t *rows_n, uint32_t n_rows_n, const uint64_t *rows_ext,
+                          uint32_t n_rows_ext)
+{
+    return ((Starks *)h)->probe_set(rows_n, n_rows_n, rows_ext, n_rows_ext);
+}
+int zkgpu_stark_probe_size(void *h, uint32_t *n_recs, uint64_t *n_words)
+{
+    return ((Starks *)h)->probe_size(n_recs, n_words);
+}
+int zkgpu_stark_probe_read(void *h, zkgpu_probe_rec *recs, uint32_t max_recs, uint64_t *payload, uint64_t max_words)
+{
+    return ((Starks *)h)->probe_read(recs, max_recs, payload, max_words);
+}
 
 // the prover's own Transcript class behind the reference's Transcript surface
 struct zkgpu_transcript {

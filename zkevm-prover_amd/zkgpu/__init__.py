@@ -90,6 +90,7 @@ _SIGS = {
     "zkgpu_rand_cols_dev": (ctypes.c_int, [vp, u64, vp, u32, u64, u64, u64]),
     "zkgpu_rand_cols_rows_dev": (ctypes.c_int, [vp, u64, vp, u32, u64, u64, u32, u64, u64]),
     "zkgpu_copy_rows_dev": (ctypes.c_int, [vp, u64, u64, vp, vp, u64, u64, u32, vp, u32, u64]),
+    "zkgpu_gather_rows_dev": (ctypes.c_int, [vp, vp, u64, u32, vp, u64]),
     "zkgpu_device_memory": (ctypes.c_int, [pu64, pu64]),
     "zkgpu_lde_workspace_bytes": (u64, [u64, u64, u64]),
     "zkgpu_zxp_eval_dev": (ctypes.c_int, [vp, u32, vp, u32, u32, u32, vp, u32, vp, vp, u32, vp, u32, vp, vp, u32,
@@ -398,6 +399,14 @@ def extend_pol_inplace_dev(base, n_ext, n, ncols):
 def set_lde_batch_cols(max_cols):
     """at most max_cols columns per extend_pol batch (0: the default)"""
     lib().zkgpu_set_lde_batch_cols(max_cols)
+
+
+def gather_rows_dev(out, src, ld, ncols, rows, nrows):
+    """out[j * ncols + c] = src[c * ld + rows[j]]: the rows `rows` (a device
+    tensor of row indices, each < ld) of a column-major section as a
+    row-major block"""
+    _check(lib().zkgpu_gather_rows_dev(_addr(out), _addr(src), ld, ncols, _addr(rows), nrows),
+           "zkgpu_gather_rows_dev")
 
 
 def rows_to_cols_dev(cols, ld, rows, nrows, ncols):

@@ -81,6 +81,9 @@ def slib():
             ("zkgpu_stark_timers", ctypes.c_int, [vp, ctypes.c_char_p, u64, vp, ctypes.c_uint32]),
             ("zkgpu_stark_destroy", None, [vp]),
             ("zkgpu_stark_last_error", ctypes.c_char_p, []),
+            ("zkgpu_stark_probe_set", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp, ctypes.c_uint32]),
+            ("zkgpu_stark_probe_size", ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(u64)]),
+            ("zkgpu_stark_probe_read", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp, u64]),
             ("zkgpu_stark_create_sharded", ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(_Info),
                                                           ctypes.POINTER(Comm)]),
             ("zkgpu_stark_memory_plan", ctypes.c_int, [ctypes.POINTER(_Info), ctypes.c_uint32,
@@ -274,6 +277,22 @@ MEM_AUTO, MEM_RESIDENT, MEM_LEAN = 0, 1, 2
 MEM_NAMES = {MEM_RESIDENT: "resident", MEM_LEAN: "lean"}
 
 
+# probe (include/zkgpu_stark.h ZKGPU_PROBE_*): the points, in proof order
+(PROBE_STEP2, PROBE_H1H2, PROBE_STEP3PREV, PROBE_Z, PROBE_STEP3, PROBE_STEP42NS, PROBE_QSPLIT,
+ PROBE_STEP52NS) = range(8)
+PROBE_POINTS = 8
+PROBE_SCALARS = 0xFFFFFFFF
+PROBE_MAX_ROWS = 4096
+PROBE_NAMES = ["step2", "h1h2", "step3prev", "z", "step3", "step42ns", "qsplit", "step52ns"]
+
+
+class ProbeRec(ctypes.Structure):
+    """zkgpu_probe_rec (include/zkgpu_stark.h); rows_off / vals_off are u64 offsets into the payload"""
+    _fields_ = [("point", ctypes.c_uint32), ("after", ctypes.c_uint32), ("section", ctypes.c_uint32),
+                ("ncols", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("rows_off", ctypes.c_uint64),
+                ("vals_off", ctypes.c_uint64)]
+
+
 def memory_plan(inst, world=0, mode=None):
     """HBM bytes per GPU of a prover of this instance (zkgpu_stark_memory_plan:
     world 0 = one GPU, W = row-sharded over W ranks; mode MEM_RESIDENT /
@@ -375,6 +394,44 @@ class GpuStark:
 
     def prove_from_rows(self, rows, register_host=False):
         return self.parse(self.prove_from_rows_raw(rows, register_host))
+
+    def probe_set(self, rows_n, rows_ext):
+        """sample these rows of the n / the extended domain around every stage
+        program of every later proof (zkgpu_stark_probe_set); both empty: off"""
+        rn = np.ascontiguousarray(rows_n, np.uint64).ravel()
+        re_ = np.ascontiguousarray(rows_ext, np.uint64).ravel()
+        _check(slib().zkgpu_stark_probe_set(self.h, rn.ctypes.data if rn.size else None, rn.size,
+                                            re_.ctypes.data if re_.size else None, re_.size),
+               "zkgpu_stark_probe_set")
+
+    def probe_size(self):
+        """(records, payload u64 words) of the last successful proof's probe; (0, 0): none"""
+        n, w = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        _check(slib().zkgpu_stark_probe_size(self.h, ctypes.byref(n), ctypes.byref(w)), "zkgpu_stark_probe_size")
+        return n.value, w.value
+
+    def probe_read_raw(self, max_recs=None, max_words=None):
+        """(zkgpu_probe_rec array, payload) of the last proof's probe (zkgpu_stark_probe_read)"""
+        n, w = self.probe_size()
+        n = n if max_recs is None else max_recs
+        w = w if max_words is None else max_words
+        recs = (ProbeRec * max(n, 1))()
+        payload = np.zeros(max(w, 1), np.uint64)
+        _check(slib().zkgpu_stark_probe_read(self.h, ctypes.cast(recs, ctypes.c_void_p), n, payload.ctypes.data, w),
+               "zkgpu_stark_probe_read")
+        return recs, payload
+
+    def probe(self):
+        """the last proof's probe: [(point, after, section, rows (n_rows,),
+        vals (n_rows, ncols))] in the order the prover took them; section
+        PROBE_SCALARS: vals[0] = challenges[24] then evals[3 n_ev]"""
+        recs, payload = self.probe_read_raw()
+        out = []
+        for r in recs[:self.probe_size()[0]]:
+            rows = payload[r.rows_off:r.rows_off + r.n_rows].copy()
+            vals = payload[r.vals_off:r.vals_off + r.n_rows * r.ncols].reshape(r.n_rows, r.ncols).copy()
+            out.append((r.point, r.after, r.section, rows, vals))
+        return out
 
     def timers(self):
         names = ctypes.create_string_buffer(4096)
