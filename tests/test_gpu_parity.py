@@ -205,7 +205,8 @@ def test_stream_marks(zkgpu):
 
 
 # ------------------------------------------------------------------ FRI
-@pytest.mark.parametrize("pol_bits,out_bits", [(6, 2), (10, 6), (12, 9), (16, 12), (20, 16), (11, 11), (13, 8)])
+@pytest.mark.parametrize("pol_bits,out_bits", [(6, 2), (10, 6), (12, 9), (16, 12), (20, 16), (11, 11), (13, 8),
+                                               (6, 5), (9, 7), (14, 13), (12, 10)])
 def test_fri_fold_vs_oracle(oracle, zkgpu, pol_bits, out_bits):
     import torch
     rng = np.random.default_rng(pol_bits * 31 + out_bits)
@@ -219,7 +220,8 @@ def test_fri_fold_vs_oracle(oracle, zkgpu, pol_bits, out_bits):
     assert np.array_equal(zkgpu.from_device(dout), oracle.fri_fold(pol, pol_bits, out_bits, sx, sinv))
 
 
-@pytest.mark.parametrize("pol_bits,out_bits,g0,ng", [(12, 8, 64, 64), (16, 12, 0, 512), (11, 7, 96, 32), (10, 5, 31, 1)])
+@pytest.mark.parametrize("pol_bits,out_bits,g0,ng", [(12, 8, 64, 64), (16, 12, 0, 512), (11, 7, 96, 32), (10, 5, 31, 1),
+                                                     (9, 8, 100, 56), (10, 8, 255, 1)])
 def test_fri_fold_rows_vs_oracle(oracle, zkgpu, pol_bits, out_bits, g0, ng):
     """zkgpu_fri_fold_rows_dev (the sharded prover's first fold): groups
     [g0, g0 + ng) from their getTransposed rows == those outputs of the

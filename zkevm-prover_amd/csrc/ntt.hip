@@ -18,6 +18,7 @@
 //   1/n * shift^k factor of the LDE is fused into the last INTT pass.
 //   n <= 4096 uses a single-workgroup-per-column LDS kernel.
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <utility>
@@ -488,6 +489,24 @@ static const char *PASS_NAMES[2][9] = {
      "k_ntt_pass<8,fwd>"},
     {"", "", "", "", "k_ntt_pass<4,inv>", "k_ntt_pass<5,inv>", "k_ntt_pass<6,inv>", "k_ntt_pass<7,inv>",
      "k_ntt_pass<8,inv>"}};
+// a non-last pass launched without its outer-twiddle table (otw == null: the
+// recurrence branch, which reads no table)
+static const char *PASS_NAMES_REC[2][9] = {
+    {"", "", "", "", "k_ntt_pass<4,fwd,rec>", "k_ntt_pass<5,fwd,rec>", "k_ntt_pass<6,fwd,rec>",
+     "k_ntt_pass<7,fwd,rec>", "k_ntt_pass<8,fwd,rec>"},
+    {"", "", "", "", "k_ntt_pass<4,inv,rec>", "k_ntt_pass<5,inv,rec>", "k_ntt_pass<6,inv,rec>",
+     "k_ntt_pass<7,inv,rec>", "k_ntt_pass<8,inv,rec>"}};
+
+// ZKGPU_NTT_OTW=0 (read per call): every non-last pass of ntt_columns takes
+// the recurrence outer twiddles instead of its table -- the branch a pass
+// over blocks above 2^OTW_MAX_LOG, or one whose table could not be allocated,
+// takes anyway.  For the tests; any other value, or unset: the tables.  The
+// 3-pass LDE keeps its tables.
+static bool otw_tables_enabled()
+{
+    const char *e = getenv("ZKGPU_NTT_OTW");
+    return !(e && strcmp(e, "0") == 0);
+}
 
 static void split_radix(uint32_t logn, uint32_t *npass, uint32_t rbits[NTT_MAX_PASSES])
 {
@@ -566,6 +585,7 @@ int ntt_columns(Ctx &ctx, uint64_t *dst, uint64_t dst_ld, const uint64_t *src, u
     a.tw_hi = ctx.tw_hi[d];
     a.logn = logn;
     split_radix(logn, &a.npass, a.rbits);
+    const bool use_otw = otw_tables_enabled();
     uint32_t logm = logn;
     for (uint32_t p = 0; p < a.npass; p++) {
         a.logm = logm;
@@ -577,7 +597,8 @@ int ntt_columns(Ctx &ctx, uint64_t *dst, uint64_t dst_ld, const uint64_t *src, u
         // factor ratio between outputs k1 + R1*k2 and k1 + R1*(k2+1): base^(R1 * n/R)
         const uint32_t rb = a.rbits[p];
         a.post_step = h_pow(post_base, (uint64_t)(1u << (rb / 2)) << (logn - rb));
-        a.otw = a.last ? nullptr : otw_table(ctx, d, logm, rb, s);
+        a.otw = (a.last || !use_otw) ? nullptr : otw_table(ctx, d, logm, rb, s);
+        const char *name = (!a.last && !a.otw) ? PASS_NAMES_REC[d][rb] : PASS_NAMES[d][rb];
         a.half_zero = 0;
         if (p == 0) {
             a.src = src;
@@ -612,7 +633,7 @@ int ntt_columns(Ctx &ctx, uint64_t *dst, uint64_t dst_ld, const uint64_t *src, u
             b.ncols = (uint32_t)nc;
             prof_begin(s);
             dispatch_pass(rb, b, nc, inverse, s);
-            prof_end(PASS_NAMES[d][rb], 8.0 * (double)(nread + n) * (double)nc, s);
+            prof_end(name, 8.0 * (double)(nread + n) * (double)nc, s);
         }
         logm -= rb;
     }
@@ -960,6 +981,10 @@ static void dispatch_strided(uint32_t la, StridedArgs a, uint64_t groups, int in
 // Measured on MI355X (2^23 -> 2^24 x 100, DESIGN.md "LDE"): 35.2 ms against
 // 33.5 ms for the 6-pass path with a third of its HBM traffic; both are VALU
 // bound, so the 6-pass path stays the default.
+// ZKGPU_NTT_OTW=0 (also read per call, otw_tables_enabled above) is the
+// other switch of this file: recurrence outer twiddles in every non-last
+// pass of ntt_columns.  It does not reach this path, whose P1 / P2 need
+// their tables.
 bool lde3_supported(uint32_t logn, uint32_t loge)
 {
     const char *e = getenv("ZKGPU_LDE3");

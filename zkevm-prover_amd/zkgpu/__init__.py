@@ -545,6 +545,11 @@ def ext_powers_dev(out, ld, base, n):
     _check(lib().zkgpu_ext_powers_dev(_addr(out), ld, b.ctypes.data, n), "zkgpu_ext_powers_dev")
 
 
+def scale_by_powers_dev(cols, ld, ncols, n, base):
+    """cols[c * ld + k] *= base^k for k < n, c < ncols, in place (canonical outputs)"""
+    _check(lib().zkgpu_scale_by_powers_dev(_addr(cols), ld, ncols, n, base), "zkgpu_scale_by_powers_dev")
+
+
 class Sections(ctypes.Structure):
     """zkgpu_sections (include/zkgpu.h): 12 column-major section bases."""
     _fields_ = [("sec", vp * 12), ("ld", u64 * 12), ("ncols", u32 * 12)]

@@ -30,7 +30,8 @@ ENV = {
     # the columns per load / LDE / leaf-absorb batch, ZKGPU_STREAM_FAIL_BATCH
     # cuts the stream short -- a profile taken with either set is not the
     # default path's)
-    "lde": ["ZKGPU_LDE3", "ZKGPU_STREAM_COLS", "ZKGPU_STREAM_FAIL_BATCH"],
+    # (ZKGPU_NTT_OTW=0: recurrence outer twiddles in every non-last NTT pass)
+    "lde": ["ZKGPU_LDE3", "ZKGPU_NTT_OTW", "ZKGPU_STREAM_COLS", "ZKGPU_STREAM_FAIL_BATCH"],
     "poseidon": [],
     # the compiler's fusion / term cap change the compiled programs (ZKGPU_ZXP_JIT,
     # interpreter vs compiled, is not one: the profiled workloads pick the
