@@ -290,7 +290,7 @@ def test_kernel_text_takes_the_intended_path(zkgpu_host, name):
 
 
 def test_fused_chains_reduce_in_time(zkgpu_host):
-    """The fused chains' own count (emit_fused, csrc/zxp_jit.hip), read off the
+    """The fused chains' own count (emit_fused, csrc/zxp_jit_source.cpp), read off the
     printed kernel: between two reductions no chain accumulator takes more
     than the cap's terms (the re-seeding lane and the constant included), for
     chains(800) and for the zkEVM-shaped FRI polynomial."""

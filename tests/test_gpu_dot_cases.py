@@ -205,3 +205,52 @@ def test_evmap_worst_case(oracle, zkgpu, n, eb, kind):
     got = zkgpu.evmap_dev([base + 8 * ne * c for c, _, _ in EV_ENTRIES], [ne] * len(EV_ENTRIES), dims, primes, dlev,
                           dlpev, n, n, eb)
     assert np.array_equal(got, want)
+
+
+# ---------------------------------------------------------------- shapes left to the interpreter
+def _shape_reference(oracle, name):
+    """(case, inputs, the oracle's sections after the program), once per shape"""
+    import jit_shape_cases as js
+    key = ("shape", name)
+    if key not in _memo:
+        c = dc.Case(name, js.UNSUPPORTED[name](), 0, 0, 0)
+        c.widths = dict(js.WIDTHS)
+        inp = dc.Inputs(c, False, seed=sum(map(ord, name)))
+        if name == "cross_row_read_after_write":
+            # Row i reads cm2[0] of row i + 1 while that row stores it (rows run
+            # in parallel, in the oracle too): the column already holds the
+            # product the program stores, so the read has one value whichever
+            # comes first -- as the stage-3 programs' shifted cells do.  Only
+            # cm3 observes this program then: a lost store to cm2[0] would not show
+            a = inp.S[js.SEC_CM1_N]
+            inp.S[js.SEC_CM2_N][:, 0] = [int(x) * int(y) % P for x, y in zip(a[:, 0], a[:, 1])]
+        _memo[key] = (c, inp, dc.oracle_eval(oracle, c, inp))
+    return _memo[key]
+
+
+@pytest.mark.parametrize("name", ["cross_row_read_after_write", "mixed_stored_triple"])
+def test_unsupported_shapes_fall_back_to_the_interpreter(oracle, zkgpu, monkeypatch, name):
+    """The two program shapes the source generator does not print
+    (tests/jit_shape_cases.py; zxp_jit_source fails on them, test_zxp_compile)
+    at 2^10 rows, where the shifted read wraps at the last row, with the
+    compiled kernels forced (ZKGPU_ZXP_JIT=2): zxp_jit_run answers 1 and the
+    interpreter runs them -- every section equals the oracle's evaluation and
+    the run with ZKGPU_ZXP_JIT=0 bit for bit.  No hiprtc runs."""
+    import jit_shape_cases as js
+    c, inp, want = _shape_reference(oracle, name)
+    with pytest.raises(RuntimeError, match="unsupported program shape"):
+        zkgpu.zxp_jit_source(c.prog, inp.chal, inp.pub, inp.evals)
+    assert not np.array_equal(want[js.SEC_CM3_N], inp.S[js.SEC_CM3_N])  # the program wrote
+    got = {}
+    for jit in ("2", "0"):
+        _set_mode(monkeypatch, ("1", "0", jit))
+        zkgpu.prof_reset()
+        zkgpu.prof_enable(True)
+        got[jit] = _run_gpu(zkgpu, c, inp, inp.S)
+        zkgpu.prof_enable(False)
+        ran = zkgpu.prof_kernels()
+        assert "k_zxp_eval" in ran and not [k for k in ran if k.startswith("k_zxp_jit")], (jit, ran)
+        for k in c.widths:
+            bad = np.argwhere(got[jit][k] != want[k])
+            assert bad.size == 0, "JIT=%s section %d: %d cells differ, first at row %d col %d" % (jit, k, len(bad), *bad[0])
+    assert all(np.array_equal(got["2"][k], got["0"][k]) for k in c.widths)

@@ -412,7 +412,7 @@ def test_full_proof_bit_exact_jit(oracle, zkgpu, monkeypatch):
 def test_fork9_widths_proof_bit_exact_jit(oracle, zkgpu, monkeypatch):
     """The fork-9-width instance (751/168/408/6 columns) with every program
     compiled: its step2 / step42ns / step52ns are block-split kernels (>= 1,000
-    instructions) with the LDS column cache (csrc/zxp_jit.hip
+    instructions) with the LDS column cache (csrc/zxp_jit_source.cpp
     lds_column_cache), the code objects prebuilt by tools/jit_prebuild.py."""
     from zkgpu.synthetic import SyntheticStark
     from zkgpu.stark import GpuStark

@@ -202,7 +202,7 @@ def test_reference_step_code(oracle, zkgpu_host, which):
 
 @pytest.mark.parametrize("name", ["step1", "step42ns", "step52ns"])
 def test_jit_source_compiles_for_gfx950(zkgpu_host, name):
-    """The straight-line kernel printed for a compiled program (csrc/zxp_jit.hip)
+    """The straight-line kernel printed for a compiled program (csrc/zxp_jit_source.cpp)
     compiles with hiprtc for gfx950 (no GPU needed); pointers and
     challenge-dependent values are not in the source."""
     from zkgpu.synthetic import SyntheticStark
@@ -218,7 +218,7 @@ def test_jit_source_compiles_for_gfx950(zkgpu_host, name):
 
 
 def test_fused_chains_only_for_fri_polynomials(zkgpu_host):
-    """Fused column chains (csrc/zxp_jit.hip): the zkEVM-shaped FRI polynomial
+    """Fused column chains (csrc/zxp_jit_source.cpp): the zkEVM-shaped FRI polynomial
     (three opening-point chains over 1,497 columns) prints its chains as loops
     reading each column once; the zkEVM-shaped quotient and the stage-3
     program (chains holding a small share of their column terms) are left
@@ -234,3 +234,35 @@ def test_fused_chains_only_for_fri_polynomials(zkgpu_host):
     for name in ("step3prev", "step42ns"):
         assert "for (int q_" not in zkgpu_host.zxp_jit_source(jp.program(0.25 if name == "step42ns" else 1.0, name),
                                                              ch, pub, ev)
+
+
+# ---------------------------------------------------------------- shapes the generator leaves to the interpreter
+def _shape_source(zkgpu_host, prog):
+    rng = np.random.default_rng(9)
+    return zkgpu_host.zxp_jit_source(prog, _rand(rng, (8, 3)), np.zeros(8, np.uint64))
+
+
+# cross_row_read_before_write: the read sees the old value of a column the
+# row writes later, but the generator decides by column, not by order -- it
+# is left to the interpreter like the read after the write
+@pytest.mark.parametrize("name", ["cross_row_read_after_write", "mixed_stored_triple", "cross_row_read_before_write"])
+def test_jit_source_unsupported_shapes(zkgpu_host, name):
+    """A cross-row read of a column the row writes (only the unshifted cell is
+    in a register) and a stored triple of which the program reads one column
+    are not printed (csrc/zxp_jit_source.cpp col_read / assign): the caller
+    runs the interpreter."""
+    import jit_shape_cases as js
+    with pytest.raises(RuntimeError, match="unsupported program shape"):
+        _shape_source(zkgpu_host, getattr(js, name)())
+
+
+@pytest.mark.parametrize("name", ["shifted_store_never_read", "shifted_store_read_back"])
+def test_jit_source_neighbouring_shapes_print(zkgpu_host, name):
+    """next to them: a shifted store to a column that is never read is stored
+    where it is assigned; a shifted cell read back in the row that wrote it
+    is forwarded, so no column read is left"""
+    import jit_shape_cases as js
+    src = _shape_source(zkgpu_host, getattr(js, name)())
+    assert "zxp_jit" in src
+    if name == "shifted_store_never_read":
+        assert "ZK_STS(" in src and ", i_0, 1);" in src

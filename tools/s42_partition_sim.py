@@ -313,7 +313,7 @@ def main():
         cp = compiled(kind)
         reads, tdeps, defs, cost = analyse(cp)
         n = len(reads)
-        S = nseg or max(1, (sum(cost) + 25000) // 50000)  # zxp_jit.hip segments_for
+        S = nseg or max(1, (sum(cost) + 25000) // 50000)  # zxp_segment.cpp segments_for
         distinct = len(set(c for r in reads for c in r))
         res = {"instructions": n, "segments": S, "distinct_cols_program": distinct,
                "col_reads_per_row": sum(len(r) for r in reads)}

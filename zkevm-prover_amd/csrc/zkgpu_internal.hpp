@@ -5,13 +5,11 @@
 
 #include "../../include/zkgpu.h"
 #include "../../include/zkgpu_zxp.h"
+#include "zxp_jit_source.hpp"  // ZxpJitIn, zxp_limbs6, the host field (gl_host.hpp)
 
 namespace zk {
 
 constexpr uint32_t NTT_MAX_PASSES = 4;  // log2 n <= 32 at radix <= 2^8
-constexpr uint32_t TW_MAX_LOG = 28;     // big-twiddle base omega_{2^28}
-constexpr uint32_t TW_LEVEL_BITS = 14;
-constexpr uint64_t TW_LEVEL_SIZE = 1ULL << TW_LEVEL_BITS;
 constexpr uint32_t POST_BITS = 12;  // LDE shift-power tables: lo 4096 entries
 
 struct Workspace {
@@ -43,12 +41,6 @@ int check_launch(const char *what);
 int check_hip(hipError_t e, const char *what);
 // grow-only scratch buffer i
 uint64_t *workspace(int i, size_t bytes);
-
-// host-side scalar Goldilocks (setup values only; all bulk math is on the GPU)
-uint64_t h_mul(uint64_t a, uint64_t b);
-uint64_t h_pow(uint64_t a, uint64_t e);
-uint64_t h_inv(uint64_t a);
-uint64_t h_w(uint32_t n);
 
 // ---- live kernel profiling (HIP events on the launch stream; zkgpu_prof_*)
 // prof_begin/prof_end bracket one kernel launch; bytes = algorithmic bytes
@@ -144,42 +136,9 @@ struct ZxpLaunch {
     double bytes;  // algorithmic bytes for profiling
 };
 // ---- zxp_jit.hip: run-time compiled straight-line expression kernels
-struct ZxpJitIn {
-    const zxp_instr *ins;  // compiled program (zkgpu_zxp_compile)
-    uint32_t n_instr;
-    const zxp_operand *opnd;
-    uint32_t n_opnd;
-    const zxp_term *terms;
-    const uint64_t *csts;
-    uint32_t n_tmp1, n_tmp3;
-    const zkgpu_sections *sections;
-    uint32_t log_dom;   // rows evaluated
-    uint32_t log_omega; // x_i = x_start * omega_{2^log_omega}^i
-    uint32_t wrap;      // shifted reads wrap mod 2^log_dom (else halo rows follow)
-    const uint64_t *challenges, *publics, *evals;  // host
-    const uint64_t *xdiv, *xdivw, *zh_dev;         // device
-    uint32_t zmask;
-    uint64_t x_start;
-    double bytes;
-    uint32_t dot_loop_min;  // DOTs with at least this many column terms loop over a table
-    uint32_t waves_per_eu;  // occupancy hint for the compiler (0: none)
-    uint32_t force_split;   // code blocks / limb chunks even below the size threshold (segments)
-    const uint64_t *scratch;  // columns of section ZXP_SEC_SCRATCH (segments, csrc/zxp_segment.hpp)
-    uint64_t scratch_ld;
-};
+// (ZxpJitIn: csrc/zxp_jit_source.hpp)
 // 0 launched, 1 shape unsupported (run the interpreter), < 0 error
 int zxp_jit_run(const ZxpJitIn &in, hipStream_t s);
-// Dot3 limbs of a canonical coefficient c: 22/21/21-bit limbs of c and of
-// c * 2^32 mod p (csrc/gl_device.hpp Dot3::term)
-inline void zxp_limbs6(uint64_t c, uint32_t out[6])
-{
-    const uint64_t v[2] = {c, h_mul(c, 1ULL << 32)};
-    for (int h = 0; h < 2; h++) {
-        out[3 * h] = (uint32_t)(v[h] & ((1u << 22) - 1));
-        out[3 * h + 1] = (uint32_t)((v[h] >> 22) & ((1u << 21) - 1));
-        out[3 * h + 2] = (uint32_t)(v[h] >> 43);
-    }
-}
 
 int rand_cols(uint64_t *base, uint64_t ld, const uint32_t *cols_dev, uint32_t ncols, uint64_t nrows, uint64_t seed,
               uint64_t stream, uint64_t row0, uint64_t rmask, hipStream_t s);

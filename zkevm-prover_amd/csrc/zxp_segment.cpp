@@ -56,6 +56,16 @@ uint32_t zxp_instr_cost(const zxp_compiled &cp, uint32_t k)
     return 7 * std::max(da, db);
 }
 
+uint32_t segments_for(const zxp_compiled &cp)
+{
+    constexpr uint64_t seg_cost = 50000;
+    constexpr uint32_t seg_min = 2000;
+    if (cp.n_instr < seg_min) return 1;
+    uint64_t cost = 0;
+    for (uint32_t k = 0; k < cp.n_instr; k++) cost += zxp_instr_cost(cp, k);
+    return (uint32_t)std::max<uint64_t>(1, (cost + seg_cost / 2) / seg_cost);
+}
+
 int zxp_segment(const zxp_compiled &cp, uint32_t n_seg, std::vector<ZxpSegment> &out, uint32_t &n_scratch)
 {
     out.clear();

@@ -30,6 +30,10 @@ struct ZxpSegment {
 // program.
 int zxp_segment(const zxp_compiled &cp, uint32_t n_seg, std::vector<ZxpSegment> &out, uint32_t &n_scratch);
 
+// Segments of a large program: one per seg_cost of estimated VALU work for
+// programs of >= seg_min compiled instructions, else 1
+uint32_t segments_for(const zxp_compiled &cp);
+
 // VALU-work estimate of one compiled instruction (cut balancing, stats)
 uint32_t zxp_instr_cost(const zxp_compiled &cp, uint32_t k);
 

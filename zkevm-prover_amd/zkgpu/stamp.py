@@ -13,7 +13,8 @@ import os
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-_COMMON = ["csrc/gl_device.hpp", "csrc/gl_rb.hpp", "csrc/zkgpu_internal.hpp", "Makefile"]
+_COMMON = ["csrc/gl_device.hpp", "csrc/gl_rb.hpp", "csrc/zkgpu_internal.hpp", "csrc/gl_host.hpp", "csrc/gl_host.cpp",
+           "Makefile"]
 FAMILIES = {
     # the NTT pass chain of extendPol (configs[1], roofline)
     "lde": _COMMON + ["csrc/ntt.hip", "csrc/api.hip"],
@@ -21,7 +22,8 @@ FAMILIES = {
     "poseidon": _COMMON + ["csrc/poseidon.hip", "csrc/poseidon_perm.hpp", "csrc/poseidon_gl_sparse.h",
                            "csrc/poseidon_gl_constants.h"],
     # the run-time compiled expression kernels (quotient / FRI polynomial)
-    "zxp": _COMMON + ["csrc/zxp_jit.hip", "csrc/zxp_compile.cpp", "csrc/zxp_segment.cpp", "csrc/zxp_segment.hpp",
+    "zxp": _COMMON + ["csrc/zxp_jit.hip", "csrc/zxp_jit_source.cpp", "csrc/zxp_jit_source.hpp", "csrc/zxp_compile.cpp",
+                      "csrc/zxp_segment.cpp", "csrc/zxp_segment.hpp",
                       "csrc/parser_convert.cpp", "csrc/parser_isa.inc", "zkgpu/synthetic_bytecode.py"],
 }
 # environment settings that change a family's kernels
