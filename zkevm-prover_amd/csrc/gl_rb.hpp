@@ -7,7 +7,28 @@
 #pragma once
 #include "gl_device.hpp"
 
+// ZKGPU_RB_MADC: the carry of t0 + hl EPS is the carry-out of the multiply-add
+// that forms hl EPS (v_mad_u64_u32 takes t0 as its 64-bit addend and writes
+// the sum's 65th bit as a lane mask to its scalar destination pair), instead
+// of a 64-bit add and a 64-bit compare behind it.  0 keeps the add-and-compare
+// form for A/B builds (tools/ab_lib.sh).
+#ifndef ZKGPU_RB_MADC
+#define ZKGPU_RB_MADC 1
+#endif
+
 namespace zk {
+
+// t + hl EPS as one multiply-add: the low 64 bits and the carry's lane mask.
+// The mask is tested by scalar code only (`cy != 0`, wave-uniform): the ISA's
+// table of required wait states has no VALU-writes-SGPR -> SALU-reads entry
+// (the scalar unit interlocks on it; the rows that exist are the VALU, VMEM
+// and lane-select readers), so none is inserted.
+__device__ __forceinline__ uint64_t gl_madc_eps(uint64_t t, uint32_t hl, uint64_t &cy)
+{
+    uint64_t r;
+    asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=&v"(r), "=&s"(cy) : "v"(hl), "v"(t));
+    return r;
+}
 
 // gl_reduce128 with the rare correction of lo - hh (a borrow needs lo < hh <
 // 2^32: about 2^-32 of products).  The subtraction is a 32-bit
@@ -25,20 +46,42 @@ __device__ __forceinline__ uint64_t gl_reduce128_rb(uint64_t lo, uint64_t hi)
     uint64_t t0 = ((uint64_t)d1 << 32) | d0, r;
     const bool br = b1 != 0;
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(br) != 0, 0)) t0 -= br ? ZK_EPS : 0ULL;
+#if ZKGPU_RB_MADC
+    // t0 + hl EPS < 2^65; after a carry r <= 2^64 - 2^33, so r + EPS cannot
+    // carry again.  The carry mask's writer and its reader are one statement
+    // with the two wait states gfx950 needs between them (the compiler does
+    // not look for hazards inside asm).
+    uint64_t cy;
+    uint32_t m;
+    asm("v_mad_u64_u32 %0, %1, %3, -1, %4\n\ts_nop 1\n\tv_cndmask_b32_e64 %2, 0, -1, %1"
+        : "=&v"(r), "=&s"(cy), "=&v"(m)
+        : "v"(hl), "v"(t0));
+    return r + m;
+#else
     const uint64_t t1 = ((uint64_t)hl << 32) - hl;
     const bool c = __builtin_add_overflow(t0, t1, &r);
     return r + (c ? ZK_EPS : 0ULL);
+#endif
 }
 
 // lo + hl 2^64 for a small hl (< 2^20: hl EPS < 2^52, so the carry needs lo
 // >= 2^64 - 2^52, about 2^-12; the Poseidon MDS row sums have hl < 2^11)
 __device__ __forceinline__ uint64_t gl_reduce96_small_rb(uint64_t lo, uint32_t hl)
 {
+#if ZKGPU_RB_MADC
+    // the carry mask is the ballot; a lane's own carry is re-derived from
+    // the wrapped sum only inside the rare branch
+    uint64_t cy;
+    uint64_t r = gl_madc_eps(lo, hl, cy);
+    if (__builtin_expect(cy != 0, 0)) r += r < lo ? ZK_EPS : 0ULL;
+    return r;
+#else
     const uint64_t t1 = ((uint64_t)hl << 32) - hl;
     uint64_t r;
     const bool c = __builtin_add_overflow(lo, t1, &r);
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(c) != 0, 0)) r += c ? ZK_EPS : 0ULL;
     return r;
+#endif
 }
 
 // Dot3::fin with the reduction's rare correction (the sum's high word is
@@ -82,10 +125,18 @@ __device__ __forceinline__ uint64_t mul2e_rb(uint64_t x)
         return mul2e<E>(x);
     } else if constexpr (E < 32) {
         const uint32_t hl = (uint32_t)(x >> (64 - E));
+#if ZKGPU_RB_MADC
+        // gl_reduce96_small_rb's shape with x << E as the addend
+        const uint64_t lo = x << E;
+        uint64_t cy;
+        uint64_t r = gl_madc_eps(lo, hl, cy);
+        if (__builtin_expect(cy != 0, 0)) r += r < lo ? ZK_EPS : 0ULL;
+#else
         const uint64_t t1 = ((uint64_t)hl << 32) - hl;
         uint64_t r;
         const bool c = __builtin_add_overflow(x << E, t1, &r);
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(c) != 0, 0)) r += c ? ZK_EPS : 0ULL;
+#endif
         return r;
     } else if constexpr (E < 64) {
         constexpr int k = E - 32;
