@@ -71,21 +71,7 @@ int main(int argc, char **argv)
         S.ld[k] = 1;
         S.ncols[k] = 0;
     }
-    ZxpJitIn J;
-    memset(&J, 0, sizeof(J));
-    J.ins = cp.instr;
-    J.n_instr = cp.n_instr;
-    J.opnd = cp.opnd;
-    J.n_opnd = cp.n_opnd;
-    J.terms = cp.term;
-    J.csts = cp.cst;
-    J.n_tmp1 = cp.n_tmp1;
-    J.n_tmp3 = cp.n_tmp3;
-    J.sections = &S;
-    J.challenges = chal.data();
-    J.publics = pub.data();
-    J.evals = ev.data();
-    zxp_jit_launch_settings(J);
+    const ZxpJitIn J = zxp_jit_in(cp, &S, chal.data(), pub.data(), ev.data());
     std::vector<ZxpSegment> seg;
     const uint32_t nseg = segments_for(cp);
     uint32_t n_scratch = 0;

@@ -67,7 +67,6 @@ uint64_t *workspace(int i, size_t bytes)
 }
 
 // ---- host scalar field: csrc/gl_host.cpp
-static const uint64_t HP = 0xFFFFFFFF00000001ULL;
 static int alloc_dev(uint64_t **p, size_t n)
 {
     if (hipMalloc((void **)p, n * sizeof(uint64_t)) != hipSuccess)
@@ -424,11 +423,6 @@ static int poseidon_one(uint64_t *out, const uint64_t *in, int full)
 
 int zkgpu_gl_poseidon_full(uint64_t out[12], const uint64_t in[12]) { return poseidon_one(out, in, 1); }
 
-static uint64_t hp_add(uint64_t a, uint64_t b)  // a, b < p
-{
-    const uint64_t s = a + b;
-    return (s < a || s >= HP) ? s - HP : s;
-}
 static uint64_t hp_pow7(uint64_t x)
 {
     const uint64_t x2 = h_mul(x, x), x3 = h_mul(x2, x), x4 = h_mul(x2, x2);
@@ -440,7 +434,7 @@ static uint64_t hp_pow7(uint64_t x)
 static void hp_full_round(uint64_t st[12], int r)
 {
     static const uint32_t MC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-    for (int i = 0; i < 12; i++) st[i] = hp_pow7(hp_add(st[i], ZKGPU_POSEIDON_RC[r * 12 + i]));
+    for (int i = 0; i < 12; i++) st[i] = hp_pow7(h_add(st[i], ZKGPU_POSEIDON_RC[r * 12 + i]));
     uint64_t t[12];
     for (int i = 0; i < 12; i++) {
         unsigned __int128 acc = (i == 0) ? (unsigned __int128)st[0] * 8 : 0;
@@ -467,19 +461,19 @@ int zkgpu_gl_poseidon_full_host(uint64_t out[12], const uint64_t in[12])
     for (int r = 0; r < 4; r++) hp_full_round(st, r);
     {
         uint64_t v[11];
-        for (int j = 0; j < 11; j++) v[j] = hp_add(st[1 + j], ZKGPU_PSP_PRE[1 + j]);
-        st[0] = hp_add(st[0], ZKGPU_PSP_PRE[0]);
+        for (int j = 0; j < 11; j++) v[j] = h_add(st[1 + j], ZKGPU_PSP_PRE[1 + j]);
+        st[0] = h_add(st[0], ZKGPU_PSP_PRE[0]);
         for (int i = 0; i < 11; i++) {
             uint64_t acc = 0;
-            for (int j = 0; j < 11; j++) acc = hp_add(acc, h_mul(v[j], ZKGPU_PSP_D0[i * 11 + j]));
+            for (int j = 0; j < 11; j++) acc = h_add(acc, h_mul(v[j], ZKGPU_PSP_D0[i * 11 + j]));
             st[1 + i] = acc;
         }
     }
     for (int k = 0; k < 22; k++) {
-        const uint64_t s0 = hp_add(hp_pow7(st[0]), ZKGPU_PSP_POST[k]);
+        const uint64_t s0 = h_add(hp_pow7(st[0]), ZKGPU_PSP_POST[k]);
         uint64_t acc = h_mul(s0, 25);
-        for (int j = 0; j < 11; j++) acc = hp_add(acc, h_mul(st[1 + j], ZKGPU_PSP_W[k * 11 + j]));
-        for (int j = 0; j < 11; j++) st[1 + j] = hp_add(st[1 + j], h_mul(s0, ZKGPU_PSP_V[k * 11 + j]));
+        for (int j = 0; j < 11; j++) acc = h_add(acc, h_mul(st[1 + j], ZKGPU_PSP_W[k * 11 + j]));
+        for (int j = 0; j < 11; j++) st[1 + j] = h_add(st[1 + j], h_mul(s0, ZKGPU_PSP_V[k * 11 + j]));
         st[0] = acc;
     }
     for (int r = 26; r < 30; r++) hp_full_round(st, r);
@@ -1075,57 +1069,6 @@ int zkgpu_device_memory(uint64_t *free_bytes, uint64_t *total_bytes)
     return 0;
 }
 
-static inline uint64_t h_add(uint64_t a, uint64_t b)
-{
-    const uint64_t s = a + b;  // a, b < p
-    return (s < a || s >= HP) ? s - HP : s;
-}
-
-// Temp-slot allocation for a ZXP program.  Program producers (the synthetic
-// builder, a chelpers converter) may give every intermediate its own temp;
-// the LDS footprint per workgroup is (slots x 64 rows x 8 B), which bounds
-// occupancy.  Each temp identity lives over [first occurrence, last
-// occurrence]; a linear scan packs the intervals of each pool (base / ext)
-// into the fewest slots.  An interval may start at the instruction where
-// another ends: the interpreter loads both sources before it stores the
-// destination.  The operand table is rewritten (duplicates are harmless).
-static void zxp_alloc_slots(const zxp_instr *in, uint32_t n_instr, std::vector<zxp_operand> &op, uint32_t &n_tmp1,
-                            uint32_t &n_tmp3)
-{
-    for (int pool = 0; pool < 2; pool++) {
-        const uint32_t kind = pool ? ZXP_TMP3 : ZXP_TMP1;
-        const uint32_t n_id = pool ? n_tmp3 : n_tmp1;
-        std::vector<uint32_t> first(n_id, UINT32_MAX), last(n_id, 0);
-        for (uint32_t k = 0; k < n_instr; k++) {
-            const uint32_t refs[3] = {in[k].dst, in[k].a, in[k].op == ZXP_COPY ? in[k].a : in[k].b};
-            for (uint32_t r : refs)
-                if (op[r].kind == kind) {
-                    const uint32_t id = op[r].a;
-                    first[id] = std::min(first[id], k);
-                    last[id] = std::max(last[id], k);
-                }
-        }
-        std::vector<uint32_t> order;
-        for (uint32_t id = 0; id < n_id; id++)
-            if (first[id] != UINT32_MAX) order.push_back(id);
-        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return first[x] < first[y]; });
-        std::vector<uint32_t> slot_of(n_id, 0), slot_end;
-        for (uint32_t id : order) {
-            uint32_t s = 0;
-            while (s < slot_end.size() && slot_end[s] > first[id]) s++;
-            if (s == slot_end.size()) slot_end.push_back(0);
-            slot_end[s] = last[id];
-            slot_of[id] = s;
-        }
-        for (auto &o : op)
-            if (o.kind == kind) o.a = slot_of[o.a];
-        const uint32_t used = (uint32_t)std::max<size_t>(slot_end.size(), 1);
-        (pool ? n_tmp3 : n_tmp1) = used;
-    }
-}
-
-// log_dom: rows evaluated (2^log_dom); log_omega: x_i = x_start * w_{2^log_omega}^i and zhInv's N =
-// 2^(log_omega - extend_bits); wrap: shifted reads wrap mod 2^log_dom, else halo rows follow the block
 // zhInv tables (<= 64 words) on the device, one per (log omega, extend
 // bits), uploaded once: the compiled expression kernels read them and need
 // no per-call upload (and no stream sync for a pageable source)
@@ -1148,311 +1091,61 @@ static const uint64_t *zh_table(uint32_t log_omega, uint32_t eb, const uint64_t 
     return d;
 }
 
-static int zxp_eval_impl(const void *instr, uint32_t n_instr, const void *opnd, uint32_t n_opnd, uint32_t n_tmp1,
-                         uint32_t n_tmp3, const zkgpu_sections *sections, uint32_t log_dom, uint32_t log_omega,
-                         int wrap, const uint64_t *challenges, const uint64_t *publics, uint32_t n_publics,
-                         const uint64_t *evals, uint32_t n_evals, const uint64_t *xdiv, const uint64_t *xdivw,
-                         uint32_t extend_bits, uint64_t x_start, int force_interp = 0)
+// One expression-program evaluation.  The host work -- argument checks, the
+// plan, the interpreter's records -- is csrc/zxp_prepare.cpp; here are the
+// device tables, the uploads and the launches.
+static int zxp_eval_run(const ZxpArgs &a)
 {
     int rc;
-    if ((rc = require_init())) return rc;
-    const uint32_t n_instr0 = n_instr, n_tmp1_0 = n_tmp1, n_tmp3_0 = n_tmp3;
-    const void *opnd0 = opnd;
-    if (log_omega > TW_MAX_LOG || log_dom > log_omega) return set_error(ZKGPU_ERR_ARG, "zxp: domain too large");
-    if (extend_bits > log_omega) return set_error(ZKGPU_ERR_ARG, "zxp: extend bits exceed the domain");
-    // validate operands on the host (no out-of-range reads in the kernel)
-    const zxp_instr *in = (const zxp_instr *)instr;
-    const zxp_operand *op = (const zxp_operand *)opnd;
-    for (uint32_t k = 0; k < n_instr; k++)
-        if (in[k].dst >= n_opnd || in[k].a >= n_opnd || (in[k].op != ZXP_COPY && in[k].b >= n_opnd) || in[k].op > 3)
-            return set_error(ZKGPU_ERR_ARG, "zxp: instruction %u out of range", k);
-    for (uint32_t k = 0; k < n_opnd; k++) {
-        const zxp_operand &o = op[k];
-        bool bad = false;
-        switch (o.kind) {
-        case ZXP_TMP1: bad = o.a >= n_tmp1; break;
-        case ZXP_TMP3: bad = o.a >= n_tmp3; break;
-        case ZXP_COL:
-        case ZXP_COL3: {
-            const uint32_t w = o.kind == ZXP_COL3 ? 3 : 1;
-            const int32_t sh = (int32_t)o.c;
-            // without wrap-around a shifted read touches halo rows [2^log_dom, 2^log_dom + sh)
-            const uint64_t need = (1ULL << log_dom) + (wrap ? 0 : (uint64_t)(sh > 0 ? sh : 0));
-            bad = o.a >= SEC_COUNT || !sections->sec[o.a] || (uint64_t)o.b + w > sections->ncols[o.a] ||
-                  sections->ld[o.a] < need || (!wrap && sh < 0);
-            break;
-        }
-        case ZXP_CHAL: bad = o.a >= 8; break;
-        case ZXP_PUB: bad = o.a >= n_publics; break;
-        case ZXP_EVAL: bad = o.a >= n_evals; break;
-        case ZXP_XDIV: bad = !xdiv; break;
-        case ZXP_XDIVW: bad = !xdivw; break;
-        case ZXP_LIT:
-        case ZXP_X:
-        case ZXP_ZI: break;
-        default: bad = true;
-        }
-        if (bad) return set_error(ZKGPU_ERR_ARG, "zxp: operand %u (kind %u) invalid", k, o.kind);
-    }
-    // compile (csrc/zxp_compile.cpp): linear-combination fusion + SSA slots.
-    // ZKGPU_ZXP_FUSE=0 runs the source program as is (slot packing only).
-    const char *env_fuse = getenv("ZKGPU_ZXP_FUSE");
-    const char *env_terms = getenv("ZKGPU_ZXP_MAX_TERMS");
-    const int fuse = env_fuse ? atoi(env_fuse) : 1;
-    const uint32_t max_terms = env_terms ? (uint32_t)atoi(env_terms) : 0u;
-    // The compiled program runs as a run-time compiled straight-line kernel
-    // (csrc/zxp_jit.hip, compiled once per program per process) on domains of
-    // 2^16 rows and more, where it pays for its ~1-2 s compile; smaller
-    // domains use the interpreter.  ZKGPU_ZXP_JIT=0 never, =2 always.
-    const char *env_jit = getenv("ZKGPU_ZXP_JIT");
-    const int jit_mode = env_jit ? atoi(env_jit) : 1;
-    // (the compiled kernels address a column with a 32-bit byte offset:
-    // domains up to 2^28 rows plus their halo)
-    const bool use_jit = !force_interp && fuse && log_dom <= 28 && (jit_mode == 2 || (jit_mode == 1 && log_dom >= 16));
-    std::vector<zxp_operand> opv;
-    const zxp_instr *pin = in;
-    const zxp_term *terms = nullptr;
-    const uint64_t *csts = nullptr;
-    uint32_t n_terms = 0;
-    if (fuse) {
-        zxp_compiled cp;
-        // (one compile serves both paths: measured, longer DOTs / fused DOT
-        // column passes / no live-temporary cap made the compiled kernels slower)
-        if ((rc = zkgpu_zxp_compile(instr, n_instr, opnd, n_opnd, n_tmp1, n_tmp3, challenges, publics, n_publics,
-                                    evals, n_evals, max_terms, &cp)))
-            return rc;
-        pin = cp.instr;
-        n_instr = cp.n_instr;
-        opv.assign(cp.opnd, cp.opnd + cp.n_opnd);
-        terms = cp.term;
-        n_terms = cp.n_term;
-        csts = cp.cst;
-        n_tmp1 = cp.n_tmp1;
-        n_tmp3 = cp.n_tmp3;
-    } else {
-        opv.assign(op, op + n_opnd);
-        zxp_alloc_slots(in, n_instr, opv, n_tmp1, n_tmp3);
-    }
-    const uint32_t n_dot_terms = [&] {
-        uint32_t c = 0;
-        for (uint32_t t = 0; t < n_terms; t++) c += terms[t].src != ZXP_TERM_ONE;
-        return c;
-    }();
-    const uint32_t n_logz = extend_bits;
-    const size_t zh = (size_t)1 << n_logz;
-    if (zh > 64) return set_error(ZKGPU_ERR_ARG, "zxp: extend bits > 6");
-    // zhInv[j] = 1/(7^N * W[eb]^j - 1)  (zhInv.cpp:7-31), N = 2^(log_dom - eb)
-    uint64_t zhv[64];
-    {
-        uint64_t sn = h_pow(7, 1ULL << (log_omega - extend_bits));
-        uint64_t we = h_w(extend_bits), w = 1;
-        for (size_t j = 0; j < zh; j++) {
-            const uint64_t x = h_mul(sn, w);  // < HP
-            zhv[j] = h_inv(x ? x - 1 : HP - 1);
-            w = h_mul(w, we);
-        }
-    }
-    for (uint32_t k = 0; k < n_opnd; k++)
-        if ((op[k].kind == ZXP_COL || op[k].kind == ZXP_COL3) && sections->ld[op[k].a] > 0xFFFFFFFFULL)
-            return set_error(ZKGPU_ERR_ARG, "zxp: section %u stride exceeds 2^32", op[k].a);
+    if ((rc = require_init()) || (rc = zxp_validate(a))) return rc;
+    ZxpPlan P;
+    if ((rc = zxp_plan(a, P))) return rc;
     hipStream_t s = g_ctx.stream;
-    // algorithmic bytes: every distinct column operand read once per row + written columns
-    double alg_bytes = 0;
-    for (uint32_t k = 0; k < n_opnd; k++) {
-        const uint32_t kind = op[k].kind;
-        alg_bytes += kind == ZXP_COL ? 1 : (kind == ZXP_COL3 || kind == ZXP_XDIV || kind == ZXP_XDIVW) ? 3 : 0;
-    }
-    alg_bytes *= 8.0 * (double)(1ULL << log_dom);
-    if (use_jit) {
+    const uint64_t x_start = a.x_start % HP;
+    if (P.jit) {
         // the compiled kernels take their own tables (csrc/zxp_jit.hip): no
         // interpreter records, no upload or stream sync here, so the host
         // prepares them while earlier work still runs on the stream
-        for (uint32_t k = 0; k < n_instr; k++) {
-            const zxp_instr &I = pin[k];
-            if (I.op == ZXP_DOT1 || I.op == ZXP_DOT3) {
-                for (uint32_t t = I.a; t < I.a + I.b; t++) {
-                    if (terms[t].src == ZXP_TERM_ONE) continue;
-                    const uint32_t kind = opv[terms[t].src].kind;
-                    if (kind != ZXP_COL && kind != ZXP_TMP1 && kind != ZXP_TMP3)
-                        return set_error(ZKGPU_ERR_ARG, "zxp: DOT term source kind %u", kind);
-                }
-            }
-            const uint32_t dk = opv[I.dst].kind;
-            if (dk != ZXP_TMP1 && dk != ZXP_TMP3 && dk != ZXP_COL && dk != ZXP_COL3)
-                return set_error(ZKGPU_ERR_ARG, "zxp: instruction %u writes a read-only operand", k);
-        }
-        const uint64_t *zh_dev = zh_table(log_omega, extend_bits, zhv, zh);
-        if (!zh_dev) return -1;
-        ZxpJitIn J;
-        J.ins = pin;
-        J.n_instr = n_instr;
-        J.opnd = opv.data();
-        J.n_opnd = (uint32_t)opv.size();
-        J.terms = terms;
-        J.csts = csts;
-        J.n_tmp1 = n_tmp1;
-        J.n_tmp3 = n_tmp3;
-        J.sections = sections;
-        J.log_dom = log_dom;
-        J.log_omega = log_omega;
-        J.wrap = wrap ? 1u : 0u;
-        J.challenges = challenges;
-        J.publics = publics;
-        J.evals = evals;
-        J.xdiv = xdiv;
-        J.xdivw = xdivw;
-        J.zh_dev = zh_dev;
-        J.zmask = (uint32_t)(zh - 1);
-        J.x_start = x_start % HP;
-        J.bytes = alg_bytes;
-        zxp_jit_launch_settings(J);
-        rc = zxp_jit_run(J, s);
-        if (rc <= 0) return rc;  // launched, or an error
-        // 1 = shape unsupported: compile for the interpreter instead
-        return zxp_eval_impl(instr, n_instr0, opnd0, n_opnd, n_tmp1_0, n_tmp3_0, sections, log_dom, log_omega, wrap,
-                             challenges, publics, n_publics, evals, n_evals, xdiv, xdivw, extend_bits, x_start, 1);
+        ZxpJitIn J = zxp_jit_in(P.prog, a.sections, a.challenges, a.publics, a.evals);
+        if (!(J.zh_dev = zh_table(a.log_omega, a.extend_bits, P.zhinv, P.n_zhinv))) return -1;
+        J.log_dom = a.log_dom;
+        J.log_omega = a.log_omega;
+        J.wrap = a.wrap ? 1u : 0u;
+        J.xdiv = a.xdiv;
+        J.xdivw = a.xdivw;
+        J.zmask = P.n_zhinv - 1;
+        J.x_start = x_start;
+        J.bytes = P.bytes;
+        if ((rc = zxp_jit_run(J, s)) <= 0) return rc;  // launched, or an error
+        // 1 = shape unsupported: the interpreter runs the same plan
     }
-    size_t off_prog = 0;
-    size_t off_terms = off_prog + (size_t)std::max<uint32_t>(n_instr, 1) * sizeof(ZOp);
-    size_t off_zh = off_terms + (size_t)n_dot_terms * sizeof(ZTerm);
-    size_t total = off_zh + zh * 8 + 16;
-    char *p = param_buf(total);
+    const size_t off_terms = (size_t)std::max<uint32_t>(P.prog.n_instr, 1) * sizeof(ZOp);
+    const size_t off_zh = off_terms + (size_t)P.n_dot_terms * sizeof(ZTerm);
+    char *p = param_buf(off_zh + P.n_zhinv * 8 + 16);
     if (!p) return set_error(ZKGPU_ERR_OOM, "param buffer");
-    const uint64_t *zh_dev = (const uint64_t *)(p + off_zh);
-    // pre-decode: resolve every operand to (kind, pointer, shift/slot, stride, immediate)
-    std::vector<ZOp> prog(n_instr);
-    auto decode = [&](const zxp_operand &o, uint32_t &kind, const uint64_t *&ptr, int32_t &ii, uint32_t &ld,
-                      uint64_t *imm) {
-        ptr = nullptr;
-        ii = 0;
-        ld = 0;
-        imm[0] = imm[1] = imm[2] = 0;
-        switch (o.kind) {
-        case ZXP_TMP1: kind = DK_T1; ii = (int32_t)(o.a * 64); break;
-        case ZXP_TMP3: kind = DK_T3; ii = (int32_t)((n_tmp1 + 3 * o.a) * 64); break;
-        case ZXP_COL:
-        case ZXP_COL3:
-            kind = o.kind == ZXP_COL ? DK_C1 : DK_C3;
-            ptr = sections->sec[o.a] + (uint64_t)o.b * sections->ld[o.a];
-            ii = (int32_t)o.c;
-            ld = (uint32_t)sections->ld[o.a];
-            break;
-        case ZXP_LIT: kind = DK_IMM1; imm[0] = ((uint64_t)o.a | ((uint64_t)o.b << 32)) % HP; break;
-        case ZXP_PUB: kind = DK_IMM1; imm[0] = publics[o.a] % HP; break;
-        case ZXP_CHAL:
-            kind = DK_IMM3;
-            for (int t = 0; t < 3; t++) imm[t] = challenges[3 * o.a + t] % HP;
-            break;
-        case ZXP_EVAL:
-            kind = DK_IMM3;
-            for (int t = 0; t < 3; t++) imm[t] = evals[3 * o.a + t] % HP;
-            break;
-        case ZXP_IMM:
-            kind = o.b == 3 ? DK_IMM3 : DK_IMM1;
-            for (int t = 0; t < 3; t++) imm[t] = csts[3 * o.a + t];
-            break;
-        case ZXP_X: kind = DK_X; break;
-        case ZXP_XDIV: kind = DK_I3; ptr = xdiv; break;
-        case ZXP_XDIVW: kind = DK_I3; ptr = xdivw; break;
-        case ZXP_ZI: kind = DK_ZI; ptr = zh_dev; ii = (int32_t)(zh - 1); break;
-        default: kind = DK_IMM1; break;
-        }
-    };
-    std::vector<ZTerm> zterms;
-    zterms.reserve(n_dot_terms);
-    for (uint32_t k = 0; k < n_instr; k++) {
-        ZOp &z = prog[k];
-        memset(&z, 0, sizeof(z));
-        z.op = pin[k].op;
-        if (z.op == ZXP_DOT1 || z.op == ZXP_DOT3) {
-            uint64_t c0[3] = {0, 0, 0};
-            z.ia = (int32_t)zterms.size();
-            for (uint32_t t = pin[k].a; t < pin[k].a + pin[k].b; t++) {
-                const zxp_term &tm = terms[t];
-                if (tm.src == ZXP_TERM_ONE) {
-                    for (int j = 0; j < 3; j++) c0[j] = h_add(c0[j], tm.coef[j] % HP);
-                    continue;
-                }
-                ZTerm zt;
-                memset(&zt, 0, sizeof(zt));
-                const zxp_operand &o = opv[tm.src];
-                if (o.kind == ZXP_COL) {
-                    zt.kind = DK_C1;
-                    zt.ptr = sections->sec[o.a] + (uint64_t)o.b * sections->ld[o.a];
-                    zt.ii = (int32_t)o.c;
-                } else if (o.kind == ZXP_TMP1) {
-                    zt.kind = DK_T1;
-                    zt.ii = (int32_t)(o.a * 64);
-                } else if (o.kind == ZXP_TMP3) {
-                    zt.kind = DK_T1;
-                    zt.ii = (int32_t)((n_tmp1 + 3 * o.a + tm.comp) * 64);
-                } else {
-                    return set_error(ZKGPU_ERR_ARG, "zxp: DOT term source kind %u", o.kind);
-                }
-                for (int j = 0; j < 3; j++) zxp_limbs6(tm.coef[j] % HP, zt.c[j]);
-                zterms.push_back(zt);
-            }
-            z.ib = (int32_t)(zterms.size() - (size_t)z.ia);
-            uint32_t *kl = reinterpret_cast<uint32_t *>(z.ima);  // 9 u32 over ima/imb
-            for (int j = 0; j < 3; j++) {
-                kl[3 * j] = (uint32_t)(c0[j] & ((1u << 22) - 1));
-                kl[3 * j + 1] = (uint32_t)((c0[j] >> 22) & ((1u << 21) - 1));
-                kl[3 * j + 2] = (uint32_t)(c0[j] >> 43);
-            }
-        } else {
-            decode(opv[pin[k].a], z.ka, z.pa, z.ia, z.lda, z.ima);
-            if (pin[k].op != ZXP_COPY) decode(opv[pin[k].b], z.kb, z.pb, z.ib, z.ldb, z.imb);
-        }
-        const uint64_t *pd;
-        uint64_t dimm[3];
-        decode(opv[pin[k].dst], z.kd, pd, z.id, z.ldd, dimm);
-        z.pd = const_cast<uint64_t *>(pd);
-        if (z.kd != DK_T1 && z.kd != DK_T3 && z.kd != DK_C1 && z.kd != DK_C3)
-            return set_error(ZKGPU_ERR_ARG, "zxp: instruction %u writes a read-only operand", k);
-        // a shifted store (the reference's parser opcodes 101-114 / 119 write
-        // pols[off + ((i + s) % N) * stride], step3.parser.cpp) lands on row
-        // (i + s) mod 2^log_dom; in a row block (no wrap-around) on local row
-        // i + s, the last s of them in the halo rows (ld checked above), which
-        // the caller hands to the next block's owner
-    }
-    if (!use_jit) {  // interpreter temporaries live in LDS
-        const uint64_t slots = (uint64_t)n_tmp1 + 3ULL * n_tmp3;
-        if (slots * 64 * 8 > 160 * 1024)
-            return set_error(ZKGPU_ERR_ARG, "zxp: %llu temp slots exceed LDS", (unsigned long long)slots);
-    }
-    if ((rc = check_hip(hipMemcpyAsync(p + off_prog, prog.data(), n_instr * sizeof(ZOp), hipMemcpyHostToDevice, s),
-                        "H2D")) ||
-        (zterms.size() &&
-         (rc = check_hip(hipMemcpyAsync(p + off_terms, zterms.data(), zterms.size() * sizeof(ZTerm),
-                                        hipMemcpyHostToDevice, s),
-                         "H2D"))) ||
-        (rc = check_hip(hipMemcpyAsync(p + off_zh, zhv, zh * 8, hipMemcpyHostToDevice, s), "H2D")))
+    std::vector<ZOp> ops;
+    std::vector<ZTerm> terms;
+    if ((rc = zxp_records(a, P, (const uint64_t *)(p + off_zh), ops, terms))) return rc;
+    if ((rc = check_hip(hipMemcpyAsync(p, ops.data(), ops.size() * sizeof(ZOp), hipMemcpyHostToDevice, s), "H2D")) ||
+        (terms.size() && (rc = check_hip(hipMemcpyAsync(p + off_terms, terms.data(), terms.size() * sizeof(ZTerm),
+                                                        hipMemcpyHostToDevice, s),
+                                         "H2D"))) ||
+        (rc = check_hip(hipMemcpyAsync(p + off_zh, P.zhinv, P.n_zhinv * 8, hipMemcpyHostToDevice, s), "H2D")))
         return rc;
-    // the sources are pageable host memory (zhv lives on this stack): the
+    // the sources are pageable host memory (the plan lives on this stack): the
     // uploads must complete before returning
     if ((rc = check_hip(hipStreamSynchronize(s), "zxp param upload"))) return rc;
     ZxpLaunch L;
-    for (int k = 0; k < SEC_COUNT; k++) {
-        L.sec[k] = sections->sec[k];
-        L.ld[k] = sections->ld[k];
-    }
-    L.prog = (const ZOp *)(p + off_prog);
+    L.prog = (const ZOp *)p;
     L.terms = (const ZTerm *)(p + off_terms);
-    L.n_instr = n_instr;
-    L.n_tmp1 = n_tmp1;
-    L.n_tmp3 = n_tmp3;
-    L.logdom = log_dom;
-    L.logomega = log_omega;
-    L.wrap = wrap ? 1u : 0u;
-    L.challenges = nullptr;
-    L.publics = nullptr;
-    L.evals = nullptr;
-    L.xdiv = xdiv;
-    L.xdivw = xdivw;
-    L.zhinv = zh_dev;
-    L.zhinv_mask = (uint32_t)(zh - 1);
-    L.x_start = x_start % HP;
-    L.bytes = alg_bytes;
+    L.n_instr = P.prog.n_instr;
+    L.n_tmp1 = P.prog.n_tmp1;
+    L.n_tmp3 = P.prog.n_tmp3;
+    L.logdom = a.log_dom;
+    L.logomega = a.log_omega;
+    L.wrap = a.wrap ? 1u : 0u;
+    L.x_start = x_start;
+    L.bytes = P.bytes;
     return zxp_eval(L, s);
 }
 
@@ -1461,8 +1154,9 @@ int zkgpu_zxp_eval_dev(const void *instr, uint32_t n_instr, const void *opnd, ui
                        const uint64_t *publics, uint32_t n_publics, const uint64_t *evals, uint32_t n_evals,
                        const uint64_t *xdiv, const uint64_t *xdivw, uint32_t extend_bits, uint64_t x_start)
 {
-    return zxp_eval_impl(instr, n_instr, opnd, n_opnd, n_tmp1, n_tmp3, sections, log_dom, log_dom, 1, challenges,
-                         publics, n_publics, evals, n_evals, xdiv, xdivw, extend_bits, x_start);
+    return zxp_eval_run(ZxpArgs{(const zxp_instr *)instr, n_instr, (const zxp_operand *)opnd, n_opnd, n_tmp1, n_tmp3,
+                                sections, log_dom, log_dom, 1, challenges, publics, n_publics, evals, n_evals, xdiv,
+                                xdivw, extend_bits, x_start});
 }
 
 int zkgpu_zxp_eval_block_dev(const void *instr, uint32_t n_instr, const void *opnd, uint32_t n_opnd, uint32_t n_tmp1,
@@ -1471,8 +1165,9 @@ int zkgpu_zxp_eval_block_dev(const void *instr, uint32_t n_instr, const void *op
                              const uint64_t *evals, uint32_t n_evals, const uint64_t *xdiv, const uint64_t *xdivw,
                              uint32_t extend_bits, uint64_t x_start)
 {
-    return zxp_eval_impl(instr, n_instr, opnd, n_opnd, n_tmp1, n_tmp3, sections, log_rows, log_domain, 0, challenges,
-                         publics, n_publics, evals, n_evals, xdiv, xdivw, extend_bits, x_start);
+    return zxp_eval_run(ZxpArgs{(const zxp_instr *)instr, n_instr, (const zxp_operand *)opnd, n_opnd, n_tmp1, n_tmp3,
+                                sections, log_rows, log_domain, 0, challenges, publics, n_publics, evals, n_evals, xdiv,
+                                xdivw, extend_bits, x_start});
 }
 
 int zkgpu_calculate_z_block_dev(uint64_t *z, uint64_t z_ld, const uint64_t *num, uint64_t num_ld, const uint64_t *den,

@@ -3,7 +3,6 @@
 
 namespace zk {
 
-static const uint64_t HP = 0xFFFFFFFF00000001ULL;
 // (a b) mod p by the Goldilocks folding 2^64 = 2^32 - 1, 2^96 = -1 (no 128-bit
 // division: the expression kernels' limb tables take ~10^5 of these per proof)
 uint64_t h_mul(uint64_t a, uint64_t b)

@@ -713,9 +713,8 @@ int zxp_eval(const ZxpLaunch &L, hipStream_t s)
     e.x_start = L.x_start;
     e.tw_lo = c.tw_lo[0];
     e.tw_hi = c.tw_hi[0];
-    const uint64_t slots = (uint64_t)L.n_tmp1 + 3ULL * L.n_tmp3;
-    size_t lds = (size_t)(slots ? slots : 1) * ZXP_THREADS * sizeof(uint64_t);
-    if (lds > 160 * 1024) return set_error(ZKGPU_ERR_ARG, "zxp: %llu temp slots exceed LDS", (unsigned long long)slots);
+    const uint64_t slots = (uint64_t)L.n_tmp1 + 3ULL * L.n_tmp3;  // within LDS: zxp_records (csrc/zxp_prepare.cpp)
+    const size_t lds = (size_t)(slots ? slots : 1) * ZXP_THREADS * sizeof(uint64_t);
     const uint64_t dom = 1ULL << L.logdom;
     prof_begin(s);
     hipLaunchKernelGGL(k_zxp_eval, dim3(nblk(dom, ZXP_THREADS)), dim3(ZXP_THREADS), lds, s, e);

@@ -1,11 +1,18 @@
-// Internal state of libzkgpu (not part of the C-ABI).
+// Internal state of libzkgpu (not part of the C-ABI): the context and the
+// launchers of the .hip files.  What needs no GPU is declared in headers
+// without HIP, which the host-only sources and the stand-alone checks under
+// tests/cpp include on their own: gl_host.hpp (the host field),
+// zxp_jit_source.hpp (the expression kernels' source generator) and
+// zxp_prepare.hpp (argument checks, plan and interpreter records of an
+// expression evaluation).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/zkgpu.h"
 #include "../../include/zkgpu_zxp.h"
-#include "zxp_jit_source.hpp"  // ZxpJitIn, zxp_limbs6, the host field (gl_host.hpp)
+#include "zxp_jit_source.hpp"  // ZxpJitIn, the host field (gl_host.hpp)
+#include "zxp_prepare.hpp"     // ZOp, ZTerm, ZxpLaunch; ZxpArgs, ZxpPlan and the phases
 
 namespace zk {
 
@@ -90,56 +97,13 @@ int fri_fold_rows(uint64_t *out, const uint64_t *rows, uint64_t g0, uint64_t n_l
                   uint32_t out_bits, const uint64_t sx[3], uint64_t shift_inv, hipStream_t s);
 int fri_transpose(uint64_t *aux, const uint64_t *pol, uint64_t degree, uint32_t tbits, hipStream_t s);
 
-// ---- stark.hip
-// Pre-decoded ZXP instruction (built on the host by zkgpu_zxp_eval_dev): every
-// operand is resolved to a source kind plus a ready pointer / shift / stride /
-// immediate, so the kernel fetches one 128-byte record per instruction with
-// wave-uniform scalar loads and no dependent descriptor or section lookups.
-enum { DK_T1 = 0, DK_T3, DK_C1, DK_C3, DK_IMM1, DK_IMM3, DK_X, DK_I3, DK_ZI };
-struct alignas(16) ZOp {
-    uint32_t op, ka, kb, kd;
-    const uint64_t *pa, *pb;
-    uint64_t *pd;
-    int32_t ia, ib, id;  // T*: slot offset (slot * 64); C*: row shift; ZI: index mask
-                         // DOT: ia = first term, ib = term count; ima/imb = constant limbs (9 u32)
-    uint32_t lda, ldb, ldd;
-    uint64_t ima[3], imb[3];
-    uint64_t pad[2];
-};
-static_assert(sizeof(ZOp) == 128, "ZOp is two 64-byte scalar loads");
-
-// ZXP_DOT term: source (a column at a row shift, or an LDS temp slot
-// component) and its F_p^3 coefficient as Dot3 limbs (3 components x 6).
-struct alignas(16) ZTerm {
-    uint32_t kind;  // DK_C1 or DK_T1
-    int32_t ii;     // C1: row shift; T1: LDS offset (slot * 64)
-    const uint64_t *ptr;
-    uint32_t c[3][6];
-    uint32_t pad[2];
-};
-static_assert(sizeof(ZTerm) == 96, "ZTerm is 96 bytes");
-
-struct ZxpLaunch {
-    uint64_t *sec[SEC_COUNT];
-    uint64_t ld[SEC_COUNT];
-    const ZOp *prog;  // device, n_instr records
-    const ZTerm *terms;  // device, DOT terms
-    uint32_t n_instr, n_tmp1, n_tmp3;
-    uint32_t logdom;    // rows evaluated
-    uint32_t logomega;  // x_i = x_start * omega_{2^logomega}^i
-    uint32_t wrap;      // shifted reads wrap mod 2^logdom (else halo rows follow)
-    const uint64_t *challenges, *publics, *evals;  // device
-    const uint64_t *xdiv, *xdivw;                  // device (2n domain) or null
-    const uint64_t *zhinv;                         // device, 2^eb entries
-    uint32_t zhinv_mask;
-    uint64_t x_start;
-    double bytes;  // algorithmic bytes for profiling
-};
 // ---- zxp_jit.hip: run-time compiled straight-line expression kernels
 // (ZxpJitIn: csrc/zxp_jit_source.hpp)
 // 0 launched, 1 shape unsupported (run the interpreter), < 0 error
 int zxp_jit_run(const ZxpJitIn &in, hipStream_t s);
 
+// ---- stark.hip
+// (the interpreter's records ZOp / ZTerm and its launch ZxpLaunch: csrc/zxp_prepare.hpp)
 int rand_cols(uint64_t *base, uint64_t ld, const uint32_t *cols_dev, uint32_t ncols, uint64_t nrows, uint64_t seed,
               uint64_t stream, uint64_t row0, uint64_t rmask, hipStream_t s);
 int copy_rows(uint64_t *dst, uint64_t dld, uint64_t drow0, const uint32_t *dcols, const uint64_t *src, uint64_t sld,

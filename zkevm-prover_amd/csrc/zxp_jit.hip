@@ -663,21 +663,7 @@ extern "C" int zkgpu_zxp_jit_source(const void *instr, uint32_t n_instr, const v
         S.ld[k] = 1;
         S.ncols[k] = 0;
     }
-    ZxpJitIn J;
-    memset(&J, 0, sizeof(J));
-    J.ins = cp.instr;
-    J.n_instr = cp.n_instr;
-    J.opnd = cp.opnd;
-    J.terms = cp.term;
-    J.csts = cp.cst;
-    J.n_tmp1 = cp.n_tmp1;
-    J.n_tmp3 = cp.n_tmp3;
-    J.sections = &S;
-    J.challenges = challenges;
-    J.publics = publics;
-    J.evals = evals;
-    J.n_opnd = cp.n_opnd;
-    zxp_jit_launch_settings(J);  // as zkgpu_zxp_eval_dev (api.hip)
+    const ZxpJitIn J = zxp_jit_in(cp, &S, challenges, publics, evals);  // as zkgpu_zxp_eval_dev (api.hip)
     std::vector<JitKernel> ks;
     static uint64_t dummy_scratch;
     const char *only_env = getenv("ZKGPU_ZXP_JIT_ONLY");

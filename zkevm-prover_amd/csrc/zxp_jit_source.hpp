@@ -48,6 +48,28 @@ inline void zxp_jit_launch_settings(ZxpJitIn &in)
     in.scratch_ld = 0;
 }
 
+// A compiled program with these settings: all the source depends on.  The
+// rest (domain, device tables, x_start, bytes) is zero for the launch to fill.
+inline ZxpJitIn zxp_jit_in(const zxp_compiled &cp, const zkgpu_sections *sections, const uint64_t *challenges,
+                           const uint64_t *publics, const uint64_t *evals)
+{
+    ZxpJitIn in{};
+    in.ins = cp.instr;
+    in.n_instr = cp.n_instr;
+    in.opnd = cp.opnd;
+    in.n_opnd = cp.n_opnd;
+    in.terms = cp.term;
+    in.csts = cp.cst;
+    in.n_tmp1 = cp.n_tmp1;
+    in.n_tmp3 = cp.n_tmp3;
+    in.sections = sections;
+    in.challenges = challenges;
+    in.publics = publics;
+    in.evals = evals;
+    zxp_jit_launch_settings(in);
+    return in;
+}
+
 // Dot3 limbs of a canonical coefficient c: 22/21/21-bit limbs of c and of
 // c * 2^32 mod p (csrc/gl_device.hpp Dot3::term)
 inline void zxp_limbs6(uint64_t c, uint32_t out[6])

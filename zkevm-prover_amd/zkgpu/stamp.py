@@ -23,7 +23,7 @@ FAMILIES = {
                            "csrc/poseidon_gl_constants.h"],
     # the run-time compiled expression kernels (quotient / FRI polynomial)
     "zxp": _COMMON + ["csrc/zxp_jit.hip", "csrc/zxp_jit_source.cpp", "csrc/zxp_jit_source.hpp", "csrc/zxp_compile.cpp",
-                      "csrc/zxp_segment.cpp", "csrc/zxp_segment.hpp",
+                      "csrc/zxp_segment.cpp", "csrc/zxp_segment.hpp", "csrc/zxp_prepare.cpp", "csrc/zxp_prepare.hpp",
                       "csrc/parser_convert.cpp", "csrc/parser_isa.inc", "zkgpu/synthetic_bytecode.py"],
 }
 # environment settings that change a family's kernels
