@@ -49,7 +49,10 @@
 //       top levels), all-gathered.
 // The constants are set up once (build / load, untimed) on a transient whole
 // copy, committed, and cut to the rank's rows.  The transcript runs on every
-// rank on identical inputs; the proof is the single-GPU proof bit for bit.
+// rank on identical inputs, and it is the same code as the single-GPU
+// prover's: Starks::prove_body is the one schedule (transcript order, stage
+// boundaries, timers), this class overrides the steps that differ.  The proof
+// is the single-GPU proof bit for bit.
 //
 // Every exchange is a zkgpu_comm call (RCCL over xGMI in production, see
 // comm_rccl.hpp; the tests plug a host-staged one); a rank never sends to
@@ -61,7 +64,7 @@ public:
     zkgpu_comm comm{};
     uint32_t W = 1, R = 0;
     uint64_t B = 0, H = 0, BH = 0;     // 2n domain: block rows, halo rows (2^blowup), ld (>= B + H)
-    uint64_t nb = 0, hn = 0, ldn = 0;  // n domain: block rows, halo rows, ld (>= nb + hn)
+    uint64_t hn = 0, ldn = 0;  // n domain (block rows: Starks::nb): halo rows, ld (>= nb + hn)
     uint64_t *ext = nullptr;    // LDE of the rank's column share (max share x NE)
     uint64_t *coln = nullptr;   // the rank's column share over all N rows (max share x N): the LDE input
     uint64_t *gath = nullptr;   // q / f gathered (3 x NE)
@@ -205,7 +208,7 @@ public:
         lo = r * base + (r < extra ? r : extra);
         hi = lo + base + (r < extra ? 1 : 0);
     }
-    uint64_t r0() const { return (uint64_t)R * nb; }  // global n-domain row of local row 0
+    uint64_t r0() const override { return (uint64_t)R * nb; }  // global n-domain row of local row 0
     uint32_t max_share() const
     {
         return std::max({1u, ceil_div(info.n_cm1, W), ceil_div(info.n_cm2, W), ceil_div(info.n_cm3, W),
@@ -448,7 +451,7 @@ public:
             for (uint32_t j : js) c.push_back(3 * p + j);
         return c;
     }
-    int quotient_sharded()
+    int quotient_pieces() override
     {
         const std::vector<uint32_t> mine = q_owned(R), my_pieces = pieces_of(mine);
         const uint64_t *qb = S.sec[SEC_Q_2NS];
@@ -469,7 +472,7 @@ public:
             if (s != R)
                 CK(zkgpu_copy_rows_dev(gath, NE, (uint64_t)s * B, nullptr, pack_r + s * stride_r, B, 0, 0, nullptr,
                                        (uint32_t)mine.size(), B));
-        // 2. the owner's pieces (quotient_pieces for its columns)
+        // 2. the owner's pieces (Starks::quotient_pieces for its columns)
         const uint64_t shift_in = pw(inv(7), N);
         for (size_t k = 0; k < mine.size(); k++) {
             const uint32_t j = mine[k];
@@ -637,11 +640,9 @@ public:
     int run_n(const Prog &p, const Stores &st, const uint64_t ch[24])
     {
         if (p.instr.empty()) return 0;
-        uint32_t log_nb = 0;
-        while ((1ULL << log_nb) < nb) log_nb++;
         const uint64_t ev0[3] = {0, 0, 0};
         CK(zkgpu_zxp_eval_block_dev(p.instr.data(), (uint32_t)p.instr.size(), p.opnd.data(), (uint32_t)p.opnd.size(),
-                                    p.n_tmp1 ? p.n_tmp1 : 1, p.n_tmp3 ? p.n_tmp3 : 1, &S, log_nb, info.n_bits, ch,
+                                    p.n_tmp1 ? p.n_tmp1 : 1, p.n_tmp3 ? p.n_tmp3 : 1, &S, log2u(nb), info.n_bits, ch,
                                     publics.data(), (uint32_t)publics.size(), ev0, 0, nullptr, nullptr, 0,
                                     pw(w_of(info.n_bits), r0())));
         if (spill(st)) return -1;
@@ -663,9 +664,7 @@ public:
     {
         uint32_t lo, hi;
         share(info.n_const, R, lo, hi);
-        if (commit_cols(trees[4], SEC_CONST_2NS, whole + (uint64_t)lo * N, N, info.n_const, verkey, nullptr, nullptr,
-                        nullptr))
-            return -1;
+        if (commit_cols(trees[4], SEC_CONST_2NS, whole + (uint64_t)lo * N, N, info.n_const, verkey, 0)) return -1;
         CK(zkgpu_copy_rows_dev(S.sec[SEC_CONST_N], ldn, 0, nullptr, whole, N, r0(), info.n_bits, nullptr,
                                info.n_const, ldn));
         CK(zkgpu_synchronize());
@@ -767,9 +766,11 @@ public:
 
     // ---- commits
     // LDE of the rank's column share (src: its first column, ld src_ld),
-    // column -> row exchange (halos packed), subtree
+    // column -> row exchange (halos packed), subtree; timers
+    // STARK_STEP_<stage>_LDE / _EXCHANGE / _MERKLETREE (stage 0, the
+    // constants: none)
     int commit_cols(Tree &t, uint32_t sec_e, const uint64_t *src, uint64_t src_ld, uint32_t ncols, uint64_t root[4],
-                    const char *lde_name, const char *xchg_name, const char *tree_name)
+                    int stage)
     {
         uint32_t lo, hi;
         share(ncols, R, lo, hi);
@@ -778,21 +779,19 @@ public:
             tstart();
             CK(zkgpu_gl_extend_pol_dev(blk, BH, src, src_ld, NE, N, ncols));
             CK(zkgpu_copy_rows_dev(blk, BH, B, nullptr, blk, BH, 0, 0, nullptr, ncols, H));
-            if (lde_name && tstop(lde_name)) return -1;
+            if (tstop_commit(stage, "LDE")) return -1;
             tstart();
             if (merkelize(t, blk, BH, ncols, root)) return -1;
-            if (tree_name && tstop(tree_name)) return -1;
-            return 0;
+            return tstop_commit(stage, "MERKLETREE");
         }
         tstart();
         if (hi > lo) CK(zkgpu_gl_extend_pol_dev(ext, NE, src, src_ld, NE, N, hi - lo));
-        if (lde_name && tstop(lde_name)) return -1;
+        if (tstop_commit(stage, "LDE")) return -1;
         tstart();
         // peer d's rows [d B, d B + B + H) (mod NE: the halo of the last
         // block wraps) of the share, packed with the block's own ld BH: the
         // message lands as whole block columns [lo, hi) on the peer
-        uint32_t log_ne = 0;
-        while ((1ULL << log_ne) < NE) log_ne++;
+        const uint32_t log_ne = log2u(NE);
         for (uint32_t d = 0; d < W; d++) {
             if (d == R || hi == lo) continue;
             CK(zkgpu_copy_rows_dev(psend(d), BH, 0, nullptr, ext, NE, (uint64_t)d * B, log_ne, nullptr,
@@ -809,23 +808,29 @@ public:
             CK(zkgpu_copy_rows_dev(blk + (uint64_t)lo * BH, BH, 0, nullptr, ext, NE, (uint64_t)R * B, log_ne, nullptr,
                                    hi - lo, B + H));
         if (exchange()) return -1;
-        if (xchg_name && tstop(xchg_name)) return -1;
+        if (tstop_commit(stage, "EXCHANGE")) return -1;
         tstart();
         if (merkelize(t, blk, BH, ncols, root)) return -1;
-        if (tree_name && tstop(tree_name)) return -1;
-        return 0;
+        return tstop_commit(stage, "MERKLETREE");
     }
 
-    // a stage's n-domain section: transpose to column shares, then commit
-    int commit_n(Tree &t, uint32_t sec_n, uint32_t sec_e, uint32_t ncols, uint64_t root[4], const char *lde_name,
-                 const char *xchg_name, const char *tree_name)
+    // stage t's commit.  t = 1, 2, 3, its n-domain section: transpose to
+    // column shares (STARK_STEP_<t>_EXCHANGE_T), then commit_cols; t = 4: the
+    // rank's row block of the quotient pieces
+    int commit_stage(int t, uint64_t root[4]) override
     {
+        if (t == 4) {
+            tstart();
+            if (merkelize(trees[3], cm4 + (uint64_t)R * B, NE, info.n_cm4, root)) return -1;
+            return tstop_commit(4, "MERKLETREE");
+        }
+        const uint32_t sec_n = SEC_CM1_N + t - 1, sec_e = SEC_CM1_2NS + t - 1, ncols = stage_cols(t);
         if (W == 1)  // the rank holds every row: no transpose
-            return commit_cols(t, sec_e, S.sec[sec_n], ldn, ncols, root, lde_name, xchg_name, tree_name);
+            return commit_cols(trees[t - 1], sec_e, S.sec[sec_n], ldn, ncols, root, t);
         tstart();
         if (rows_to_share(sec_n, ncols)) return -1;
-        if (xchg_name && tstop((std::string(xchg_name) + "_T").c_str())) return -1;
-        return commit_cols(t, sec_e, coln, N, ncols, root, lde_name, xchg_name, tree_name);
+        if (tstop_commit(t, "EXCHANGE_T")) return -1;
+        return commit_cols(trees[t - 1], sec_e, coln, N, ncols, root, t);
     }
 
     bool fri_sharded(uint64_t ngroups) const { return W > 1 && ngroups % W == 0 && ngroups / W >= 2; }
@@ -910,8 +915,7 @@ public:
     {
         if (!fri_sharded(ngroups)) return Starks::fri_open(si, ngroups, width, yq, vals, sibs);
         const uint64_t bl = ngroups / W, levels = fri_steps[si];
-        uint32_t log_b = 0;
-        while ((1ULL << log_b) < bl) log_b++;
+        const uint32_t log_b = log2u(bl);
         const uint64_t rec = width + 4 * levels;
         const Tree &t = ftrees[si];
         std::vector<uint64_t> mine((uint64_t)q() * rec, 0), own, local;
@@ -1137,118 +1141,55 @@ public:
     int run_block(const Prog &p, const uint64_t ch[24], const uint64_t *evals, uint32_t n_ev, const uint64_t *xd,
                   const uint64_t *xdw)
     {
-        uint32_t log_b = 0;
-        while ((1ULL << log_b) < B) log_b++;
         const uint64_t x0 = mul(7, pw(w_of(info.n_bits_ext), (uint64_t)R * B));
         CK(zkgpu_zxp_eval_block_dev(p.instr.data(), (uint32_t)p.instr.size(), p.opnd.data(), (uint32_t)p.opnd.size(),
-                                    p.n_tmp1 ? p.n_tmp1 : 1, p.n_tmp3 ? p.n_tmp3 : 1, &S, log_b, info.n_bits_ext, ch,
+                                    p.n_tmp1 ? p.n_tmp1 : 1, p.n_tmp3 ? p.n_tmp3 : 1, &S, log2u(B), info.n_bits_ext, ch,
                                     publics.data(), (uint32_t)publics.size(), evals, n_ev, xd, xdw, eb, x0));
+        return 0;
+    }
+
+    // ---- the steps of Starks::prove_body on the rank's rows (with
+    // commit_stage, quotient_pieces, h1h2_all, z_all and ncol above)
+    int run_prog(uint32_t point, const Prog &p, const uint64_t ch[24], const std::vector<uint64_t> &evals) override
+    {
+        switch (point) {
+        case ZKGPU_PROBE_STEP2: return run_n(p, st2, ch);
+        case ZKGPU_PROBE_STEP3PREV: return run_n(p, st3p, ch);
+        case ZKGPU_PROBE_STEP3: return run_n(p, st3, ch);
+        case ZKGPU_PROBE_STEP42NS: return run_block(p, ch, evals.data(), 0, nullptr, nullptr);
+        }
+        const uint64_t xo = 3ULL * R * B;  // step52ns; xdiv rows are interleaved F_p^3
+        return run_block(p, ch, evals.data(), info.n_ev, xdiv + xo, xdivw + xo);
+    }
+    // the ranks' partial sums all-gathered and added mod p
+    int sum_evals(std::vector<uint64_t> &evals) override
+    {
+        std::vector<uint64_t> all;
+        if (allgather(evals.data(), evals.size(), all)) return -1;
+        for (size_t i = 0; i < evals.size(); i++) {
+            unsigned __int128 acc = 0;
+            for (uint32_t s = 0; s < W; s++) acc += all[s * evals.size() + i];
+            evals[i] = (uint64_t)(acc % P);
+        }
+        return 0;
+    }
+    int xdivxsub(const uint64_t xi[3]) override
+    {
+        CK(zkgpu_xdivxsub_rows_dev(xdiv, xdivw, xi, info.n_bits, info.n_bits_ext, (uint64_t)R * B, B));
+        return 0;
+    }
+    int fill_fri_pol0() override
+    {
+        if (fri_first_sharded()) return 0;  // f stays in row blocks (fri_transpose_layer)
+        if (gather_rows(S.sec[SEC_F_2NS], gath)) return -1;
+        CK(zkgpu_cols3_to_interleaved_dev(fri_pol[0], gath, NE, NE));
         return 0;
     }
 
     int prove(uint64_t *out) override
     {
-        const int rc = abort_comm(prove_sharded(out));
-        const int rc2 = take_cm1_async(true);  // a queued trace becomes cm1_n (set_cm1_async)
-        return rc ? rc : rc2;
-    }
-
-    int prove_sharded(uint64_t *out)
-    {
-        timers.clear();
-        pend_t.clear();
-        pend_x.clear();
-        n_marks = 0;
         n_exch = sent_bytes = max_sent = 0;
-        auto tall = clk::now();
-        Transcript tr;
-        tr.put(verkey, 4);
-        tr.put(publics.data(), publics.size());
-        uint64_t ch[24] = {0};
-        uint64_t roots[4][4];
-        std::vector<uint64_t> evals(3 * info.n_ev);
-        // STAGE 1 (starks.cpp:49-63)
-        if (commit_n(trees[0], SEC_CM1_N, SEC_CM1_2NS, info.n_cm1, roots[0], "STARK_STEP_1_LDE",
-                     "STARK_STEP_1_EXCHANGE", "STARK_STEP_1_MERKLETREE"))
-            return -1;
-        tr.put(roots[0], 4);
-        // STAGE 2 (:65-144), n domain on the rank's rows
-        tr.get_field(ch + 0);
-        tr.get_field(ch + 3);
-        tstart();
-        if (run_n(step2, st2, ch)) return -1;
-        if (tstop("STARK_STEP_2_CALCULATE_EXPS")) return -1;
-        if (info.n_pu) {
-            tstart();
-            if (h1h2_all()) return -1;
-            if (tstop("STARK_STEP_2_CALCULATEH1H2")) return -1;
-        }
-        if (commit_n(trees[1], SEC_CM2_N, SEC_CM2_2NS, info.n_cm2, roots[1], "STARK_STEP_2_LDE",
-                     "STARK_STEP_2_EXCHANGE", "STARK_STEP_2_MERKLETREE"))
-            return -1;
-        tr.put(roots[1], 4);
-        // STAGE 3 (:146-224)
-        tr.get_field(ch + 6);
-        tr.get_field(ch + 9);
-        tstart();
-        if (run_n(step3prev, st3p, ch)) return -1;
-        if (tstop("STARK_STEP_3_CALCULATE_EXPS")) return -1;
-        tstart();
-        if (z_all()) return -1;
-        if (tstop("STARK_STEP_3_CALCULATE_Z")) return -1;
-        if (!step3.instr.empty()) {
-            tstart();
-            if (run_n(step3, st3, ch)) return -1;
-            if (tstop("STARK_STEP_3_CALCULATE_EXPS_2")) return -1;
-        }
-        if (commit_n(trees[2], SEC_CM3_N, SEC_CM3_2NS, info.n_cm3, roots[2], "STARK_STEP_3_LDE",
-                     "STARK_STEP_3_EXCHANGE", "STARK_STEP_3_MERKLETREE"))
-            return -1;
-        tr.put(roots[2], 4);
-        // STAGE 4 (:226-296): the quotient on the rank's rows
-        tr.get_field(ch + 12);
-        tstart();
-        if (run_block(step42ns, ch, evals.data(), 0, nullptr, nullptr)) return -1;
-        if (tstop("STARK_STEP_4_CALCULATE_EXPS_2NS")) return -1;
-        tstart();
-        if (quotient_sharded()) return -1;
-        if (tstop("STARK_STEP_4_CALCULATE_EXPS_2NS_INTT_NTT")) return -1;
-        tstart();
-        if (merkelize(trees[3], cm4 + (uint64_t)R * B, NE, info.n_cm4, roots[3])) return -1;
-        if (tstop("STARK_STEP_4_MERKLETREE")) return -1;
-        tr.put(roots[3], 4);
-        // STAGE 5 (:298-392)
-        tstart();
-        uint64_t *xi = ch + 21;
-        tr.get_field(xi);
-        if (lagrange_xi(xi, r0(), nb)) return -1;  // the rank's rows only
-        if (tstop("STARK_STEP_5_LEv_LpEv")) return -1;
-        tstart();
-        {
-            std::vector<uint64_t> part(3 * info.n_ev), all;
-            if (evmap_rows(r0(), nb, part.data()) || allgather(part.data(), part.size(), all)) return -1;
-            for (size_t i = 0; i < evals.size(); i++) {
-                unsigned __int128 acc = 0;
-                for (uint32_t s = 0; s < W; s++) acc += all[s * evals.size() + i];
-                evals[i] = (uint64_t)(acc % P);
-            }
-        }
-        if (tstop("STARK_STEP_5_EVMAP")) return -1;
-        tr.put(evals.data(), evals.size());
-        tr.get_field(ch + 15);
-        tr.get_field(ch + 18);
-        tstart();
-        CK(zkgpu_xdivxsub_rows_dev(xdiv, xdivw, xi, info.n_bits, info.n_bits_ext, (uint64_t)R * B, B));
-        if (tstop("STARK_STEP_5_XDIVXSUB")) return -1;
-        tstart();
-        const uint64_t xo = 3ULL * R * B;  // xdiv rows are interleaved F_p^3
-        if (run_block(step52ns, ch, evals.data(), info.n_ev, xdiv + xo, xdivw + xo)) return -1;
-        if (!fri_first_sharded()) {  // else f stays in row blocks (fri_transpose_layer)
-            if (gather_rows(S.sec[SEC_F_2NS], gath)) return -1;
-            CK(zkgpu_cols3_to_interleaved_dev(fri_pol[0], gath, NE, NE));
-        }
-        if (tstop("STARK_STEP_5_CALCULATE_EXPS")) return -1;
-        const int rc = fri_and_queries(tr, &roots[0][0], evals, out, tall);
+        const int rc = abort_comm(prove_body(out));
         // a count, not a time: the largest exchange this rank posted (every
         // exchange is at most one send and one receive per peer, 2 (W - 1))
         // and the communicator's world and this proof's exchange volume
@@ -1261,7 +1202,8 @@ public:
             timers.emplace_back("COUNT_COMM_BYTES_SENT", (double)sent_bytes);
             timers.emplace_back("COUNT_COMM_MAX_BYTES_SENT", (double)max_sent);
         }
-        return rc;
+        const int rc2 = take_cm1_async(true);  // a queued trace becomes cm1_n (set_cm1_async)
+        return rc ? rc : rc2;
     }
 
     // each query row is opened by the rank owning it, the records all-gathered
@@ -1269,8 +1211,7 @@ public:
     {
         const uint32_t widths[5] = {info.n_cm1, info.n_cm2, info.n_cm3, info.n_cm4, info.n_const};
         const uint64_t rec = s0_record();
-        uint32_t log_b = 0;
-        while ((1ULL << log_b) < B) log_b++;
+        const uint32_t log_b = log2u(B);
         std::vector<uint64_t> mine((uint64_t)q() * rec, 0), own, local;
         for (uint32_t qi = 0; qi < q(); qi++)
             if (ys[qi] / B == R) {

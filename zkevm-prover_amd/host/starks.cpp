@@ -58,6 +58,12 @@ static uint64_t pw(uint64_t a, uint64_t e)
     return r;
 }
 static uint64_t inv(uint64_t a) { return pw(a, P - 2); }
+static uint32_t log2u(uint64_t x)  // the least k with 2^k >= x
+{
+    uint32_t k = 0;
+    while ((1ULL << k) < x) k++;
+    return k;
+}
 static uint64_t w_of(uint32_t n)  // Goldilocks::w(n)
 {
     uint64_t w = 7277203076849721926ULL;
@@ -162,6 +168,9 @@ public:
     Prog step0, step1, step2, step3prev, step3, step42ns, step52ns;
     uint64_t N = 0, NE = 0;
     uint32_t eb = 0;
+    // the n-domain rows [r0(), r0() + nb) of LEv / LpEv and evmap: all N (a rank of the sharded prover: its block)
+    uint64_t nb = 0;
+    virtual uint64_t r0() const { return 0; }
     zkgpu_sections S;
     std::vector<void *> allocs;
     uint64_t *nodes[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -477,7 +486,7 @@ public:
         for (uint32_t si = 1; si < in->n_fri_steps; si++)
             if (in->fri_steps[si] >= in->fri_steps[si - 1] || in->fri_steps[si - 1] - in->fri_steps[si] > 5)
                 return fail("stark_create: FRI steps must decrease by 1..5 bits");
-        N = 1ULL << in->n_bits;
+        N = nb = 1ULL << in->n_bits;
         NE = 1ULL << in->n_bits_ext;
         eb = in->n_bits_ext - in->n_bits;
         if (init) CK(zkgpu_init(-1));
@@ -792,6 +801,12 @@ public:
         timers.emplace_back(name, std::chrono::duration<double, std::milli>(clk::now() - t0).count());
         return 0;
     }
+    // a commit's timers, STARK_STEP_<stage>_<what>; stage 0 (the constants'
+    // commit, outside any proof): no timer
+    int tstop_commit(int stage, const char *what)
+    {
+        return stage ? tstop(("STARK_STEP_" + std::to_string(stage) + "_" + what).c_str()) : 0;
+    }
     // exchanges of a sharded proof: (marks, bytes sent) -> the total device
     // time inside them and that of the largest one
     std::vector<std::pair<std::pair<uint32_t, uint32_t>, uint64_t>> pend_x;
@@ -821,37 +836,25 @@ public:
         return 0;
     }
 
-    // extendPol of an n-domain section into its extended one, then its tree;
-    // in place (lean plan: the section's n-domain values sit at the start of
-    // its extended region) when the two pointers are equal
-    int commit(int t, uint32_t sec_n, uint32_t sec_e, uint32_t ncols, Transcript &tr, uint64_t root[4],
-               const char *lde_name, const char *tree_name)
+    // the committed columns of stage t = 1 .. 4 (cm1 .. cm4), sections
+    // SEC_CM1_2NS + t - 1 and, for t < 4, SEC_CM1_N + t - 1
+    uint32_t stage_cols(int t) const
     {
-        tstart();
-        if (S.sec[sec_e] == S.sec[sec_n])
-            CK(zkgpu_gl_extend_pol_inplace_dev(S.sec[sec_e], NE, N, ncols));
-        else
-            CK(zkgpu_gl_extend_pol_dev(S.sec[sec_e], NE, S.sec[sec_n], N, NE, N, ncols));
-        if (tstop(lde_name)) return -1;
-        tstart();
-        CK(zkgpu_gl_merkletree_dev(nodes[t], S.sec[sec_e], NE, ncols, NE));
-        CK(zkgpu_memcpy_d2h(root, nodes[t] + zkgpu_gl_merkle_num_elements(NE) - 4, 32));
-        if (tstop(tree_name)) return -1;
-        tr.put(root, 4);
-        return 0;
+        const uint32_t w[4] = {info.n_cm1, info.n_cm2, info.n_cm3, info.n_cm4};
+        return w[t - 1];
     }
 
     // lean plan, stage 1: cm1's extension into the scratch above cm1_n
     // (columns [0, split), hashed and dropped) and into `keep` (the rest,
     // kept for stage 4), one tree over both regions
-    int commit_cm1_lean(Transcript &tr, uint64_t root[4])
+    int commit_cm1_lean(uint64_t root[4])
     {
         const uint64_t W1 = info.n_cm1, split = W1 - keep_cols;
         S.sec[SEC_CM1_2NS] = cm1_early;
         tstart();
         if (split) CK(zkgpu_gl_extend_pol_dev(cm1_early, NE, arena, N, NE, N, split));
         if (keep_cols) CK(zkgpu_gl_extend_pol_dev(keep, NE, arena + split * N, N, NE, N, keep_cols));
-        if (tstop("STARK_STEP_1_LDE")) return -1;
+        if (tstop_commit(1, "LDE")) return -1;
         tstart();
         if (!keep_cols)
             CK(zkgpu_gl_merkletree_dev(nodes[0], cm1_early, NE, W1, NE));
@@ -860,9 +863,7 @@ public:
         else
             CK(zkgpu_gl_merkletree2_dev(nodes[0], cm1_early, keep, NE, split, W1, NE));
         CK(zkgpu_memcpy_d2h(root, nodes[0] + zkgpu_gl_merkle_num_elements(NE) - 4, 32));
-        if (tstop("STARK_STEP_1_MERKLETREE")) return -1;
-        tr.put(root, 4);
-        return 0;
+        return tstop_commit(1, "MERKLETREE");
     }
 
     // columns per batch of the streamed stage 1, a multiple of 8 (the linear
@@ -890,7 +891,7 @@ public:
     // absorbs it into tree 1's leaf sponge while the later batches load.
     // Loads and compute are queued from this one thread: every wait is queued
     // after the record it waits for.  A failure leaves cm1_broken set.
-    int commit_cm1_stream(Transcript &tr, uint64_t root[4])
+    int commit_cm1_stream(uint64_t root[4])
     {
         const uint64_t W1 = info.n_cm1, split = lean() ? W1 - keep_cols : W1, B = stream_batch_cols();
         if (lean()) S.sec[SEC_CM1_2NS] = cm1_early;
@@ -925,17 +926,7 @@ public:
         }
         if (rc_close) return fail("prove_from_rows: %s", zkgpu_last_error());
         cm1_broken = false;
-        if (tstop("STARK_STEP_1_STREAM")) return -1;
-        tr.put(root, 4);
-        return 0;
-    }
-
-    // STAGE 1 (starks.cpp:49-63)
-    int stage1(Transcript &tr, uint64_t root[4])
-    {
-        if (stream_rows) return commit_cm1_stream(tr, root);
-        if (lean()) return commit_cm1_lean(tr, root);
-        return commit(0, SEC_CM1_N, SEC_CM1_2NS, info.n_cm1, tr, root, "STARK_STEP_1_LDE", "STARK_STEP_1_MERKLETREE");
+        return tstop("STARK_STEP_1_STREAM");
     }
 
     // one proof of the executor's host buffer: set_cm1(rows) + prove() with
@@ -1149,12 +1140,6 @@ public:
         }
         return 0;
     }
-    int probed_run(uint32_t point, const Prog &p, bool ext, const uint64_t ch[24], const std::vector<uint64_t> &evals,
-                   uint32_t n_ev)
-    {
-        if (probe_point(point, 0, ch, evals) || run(p, ext, ch, evals.data(), n_ev)) return -1;
-        return probe_point(point, 1, ch, evals);
-    }
     // after the proof's last kernel and its total timer: the one copy to the host
     int probe_readback()
     {
@@ -1186,6 +1171,63 @@ public:
         return 0;
     }
 
+    // ---- the steps of prove_body that the row-sharded prover overrides
+    // (with quotient_pieces, h1h2_all, z_all, ncol, r0 and the FRI steps)
+
+    // The commit of stage t.  t = 1, 2, 3: extendPol of the stage's n-domain
+    // section into its extended one (stage 1 of a streamed or a lean proof in
+    // its own way) -- in place (lean plan: the n-domain values sit at the
+    // start of the extended region) when the two pointers are equal --, then
+    // its tree and root; t = 4, the quotient pieces: tree and root.
+    virtual int commit_stage(int t, uint64_t root[4])
+    {
+        if (t == 1 && stream_rows) return commit_cm1_stream(root);
+        if (t == 1 && lean()) return commit_cm1_lean(root);
+        const uint32_t sec_e = SEC_CM1_2NS + t - 1, ncols = stage_cols(t);
+        if (t < 4) {
+            const uint32_t sec_n = SEC_CM1_N + t - 1;
+            tstart();
+            if (S.sec[sec_e] == S.sec[sec_n])
+                CK(zkgpu_gl_extend_pol_inplace_dev(S.sec[sec_e], NE, N, ncols));
+            else
+                CK(zkgpu_gl_extend_pol_dev(S.sec[sec_e], NE, S.sec[sec_n], N, NE, N, ncols));
+            if (tstop_commit(t, "LDE")) return -1;
+        }
+        tstart();
+        CK(zkgpu_gl_merkletree_dev(nodes[t - 1], S.sec[sec_e], NE, ncols, NE));
+        CK(zkgpu_memcpy_d2h(root, nodes[t - 1] + zkgpu_gl_merkle_num_elements(NE) - 4, 32));
+        return tstop_commit(t, "MERKLETREE");
+    }
+    // The stage program p of probe point `point`: ZKGPU_PROBE_STEP2 /
+    // STEP3PREV / STEP3 on the n domain, STEP42NS / STEP52NS on the extended
+    // one (the last reads the evaluations); here between its two probe points.
+    virtual int run_prog(uint32_t point, const Prog &p, const uint64_t ch[24], const std::vector<uint64_t> &evals)
+    {
+        const bool ext = point == ZKGPU_PROBE_STEP42NS || point == ZKGPU_PROBE_STEP52NS;
+        const uint32_t n_ev = point == ZKGPU_PROBE_STEP52NS ? info.n_ev : 0;
+        if (probe_point(point, 0, ch, evals) || run(p, ext, ch, evals.data(), n_ev)) return -1;
+        return probe_point(point, 1, ch, evals);
+    }
+    // evmap's sums over rows [r0(), r0() + nb) -> the evaluations (all rows: they are)
+    virtual int sum_evals(std::vector<uint64_t> &) { return 0; }
+    virtual int xdivxsub(const uint64_t xi[3])
+    {
+        CK(zkgpu_xdivxsub_dev(xdiv, xdivw, xi, info.n_bits, info.n_bits_ext));
+        return 0;
+    }
+    // the FRI polynomial (SEC_F_2NS, 3 columns) interleaved into fri_pol[0]
+    virtual int fill_fri_pol0()
+    {
+        CK(zkgpu_cols3_to_interleaved_dev(fri_pol[0], S.sec[SEC_F_2NS], NE, NE));
+        return 0;
+    }
+
+    // The one Fiat-Shamir schedule of the single-GPU and the row-sharded
+    // prover: the order of the transcript's inputs and challenges, the stage
+    // boundaries and the stage timers (the FRI part: fri_and_queries).  The
+    // row-sharded prover is never lean (shape() leaves mem_mode RESIDENT) and
+    // refuses probe_set and prove_from_rows: the lean(), probe_recs and
+    // stream_rows branches are dead there.
     int prove_body(uint64_t *out)
     {
         probe_valid = false;
@@ -1200,7 +1242,13 @@ public:
         uint64_t ch[24] = {0};
         uint64_t roots[4][4];
         std::vector<uint64_t> evals(3 * info.n_ev);
-        if (stage1(tr, roots[0])) return -1;
+        auto commit_root = [&](int t) {  // stage t's commit, its root into the transcript
+            if (commit_stage(t, roots[t - 1])) return -1;
+            tr.put(roots[t - 1], 4);
+            return 0;
+        };
+        // STAGE 1 (starks.cpp:49-63)
+        if (commit_root(1)) return -1;
         // lean: the regions of tmpExp_n / cm2_n / cm3_n held other sections;
         // the columns no stage writes read 0, as under the resident plan
         if (lean() && (zero_unwritten(SEC_TMP_N) || zero_unwritten(SEC_CM2_N) || zero_unwritten(SEC_CM3_N)))
@@ -1216,7 +1264,7 @@ public:
         tr.get_field(ch + 0);
         tr.get_field(ch + 3);
         tstart();
-        if (probed_run(ZKGPU_PROBE_STEP2, step2, false, ch, evals, 0)) return -1;
+        if (run_prog(ZKGPU_PROBE_STEP2, step2, ch, evals)) return -1;
         if (tstop("STARK_STEP_2_CALCULATE_EXPS")) return -1;
         if (info.n_pu) {
             tstart();
@@ -1225,13 +1273,12 @@ public:
                 return -1;
             if (tstop("STARK_STEP_2_CALCULATEH1H2")) return -1;
         }
-        if (commit(1, SEC_CM2_N, SEC_CM2_2NS, info.n_cm2, tr, roots[1], "STARK_STEP_2_LDE", "STARK_STEP_2_MERKLETREE"))
-            return -1;
+        if (commit_root(2)) return -1;
         // STAGE 3 (:146-224)
         tr.get_field(ch + 6);
         tr.get_field(ch + 9);
         tstart();
-        if (probed_run(ZKGPU_PROBE_STEP3PREV, step3prev, false, ch, evals, 0)) return -1;
+        if (run_prog(ZKGPU_PROBE_STEP3PREV, step3prev, ch, evals)) return -1;
         if (tstop("STARK_STEP_3_CALCULATE_EXPS")) return -1;
         tstart();
         if (probe_point(ZKGPU_PROBE_Z, 0, ch, evals) || z_all() || probe_point(ZKGPU_PROBE_Z, 1, ch, evals)) return -1;
@@ -1239,11 +1286,10 @@ public:
         // step3: post-Z expressions (starks.cpp:193-208)
         if (!step3.instr.empty()) {
             tstart();
-            if (probed_run(ZKGPU_PROBE_STEP3, step3, false, ch, evals, 0)) return -1;
+            if (run_prog(ZKGPU_PROBE_STEP3, step3, ch, evals)) return -1;
             if (tstop("STARK_STEP_3_CALCULATE_EXPS_2")) return -1;
         }
-        if (commit(2, SEC_CM3_N, SEC_CM3_2NS, info.n_cm3, tr, roots[2], "STARK_STEP_3_LDE", "STARK_STEP_3_MERKLETREE"))
-            return -1;
+        if (commit_root(3)) return -1;
         // STAGE 4 (:226-296)
         tr.get_field(ch + 12);
         if (lean()) {
@@ -1258,18 +1304,14 @@ public:
             if (tstop("STARK_STEP_4_CM1_LDE")) return -1;
         }
         tstart();
-        if (probed_run(ZKGPU_PROBE_STEP42NS, step42ns, true, ch, evals, 0)) return -1;
+        if (run_prog(ZKGPU_PROBE_STEP42NS, step42ns, ch, evals)) return -1;
         if (tstop("STARK_STEP_4_CALCULATE_EXPS_2NS")) return -1;
         tstart();
-        if (probe_point(ZKGPU_PROBE_QSPLIT, 0, ch, evals) || quotient_pieces(S.sec[SEC_Q_2NS], S.sec[SEC_CM4_2NS]) ||
+        if (probe_point(ZKGPU_PROBE_QSPLIT, 0, ch, evals) || quotient_pieces() ||
             probe_point(ZKGPU_PROBE_QSPLIT, 1, ch, evals))
             return -1;
         if (tstop("STARK_STEP_4_CALCULATE_EXPS_2NS_INTT_NTT")) return -1;
-        tstart();
-        CK(zkgpu_gl_merkletree_dev(nodes[3], S.sec[SEC_CM4_2NS], NE, info.n_cm4, NE));
-        CK(zkgpu_memcpy_d2h(roots[3], nodes[3] + zkgpu_gl_merkle_num_elements(NE) - 4, 32));
-        if (tstop("STARK_STEP_4_MERKLETREE")) return -1;
-        tr.put(roots[3], 4);
+        if (commit_root(4)) return -1;
         // STAGE 5 (:298-392)
         tstart();
         uint64_t *xi = ch + 21;
@@ -1285,23 +1327,22 @@ public:
             // the extended rows k << eb are the points 7 w_N^k: the weights of
             // xi / 7 (starks.cpp:316-322)
             const uint64_t i7 = inv(7), xs[3] = {mul(xi[0], i7), mul(xi[1], i7), mul(xi[2], i7)};
-            if (lagrange_xi(xs, 0, N)) return -1;
-        } else if (lagrange_xi(xi, 0, N)) {
+            if (lagrange_xi(xs, r0(), nb)) return -1;
+        } else if (lagrange_xi(xi, r0(), nb)) {
             return -1;
         }
         if (tstop("STARK_STEP_5_LEv_LpEv")) return -1;
         tstart();
-        if (evmap_rows(0, N, evals.data())) return -1;
+        if (evmap_rows(r0(), nb, evals.data()) || sum_evals(evals)) return -1;
         if (tstop("STARK_STEP_5_EVMAP")) return -1;
         tr.put(evals.data(), evals.size());
         tr.get_field(ch + 15);
         tr.get_field(ch + 18);
         tstart();
-        CK(zkgpu_xdivxsub_dev(xdiv, xdivw, xi, info.n_bits, info.n_bits_ext));
+        if (xdivxsub(xi)) return -1;
         if (tstop("STARK_STEP_5_XDIVXSUB")) return -1;
         tstart();
-        if (probed_run(ZKGPU_PROBE_STEP52NS, step52ns, true, ch, evals, info.n_ev)) return -1;
-        CK(zkgpu_cols3_to_interleaved_dev(fri_pol[0], S.sec[SEC_F_2NS], NE, NE));
+        if (run_prog(ZKGPU_PROBE_STEP52NS, step52ns, ch, evals) || fill_fri_pol0()) return -1;
         if (tstop("STARK_STEP_5_CALCULATE_EXPS")) return -1;
         if (fri_and_queries(tr, &roots[0][0], evals, out, tall)) return -1;
         return probe_readback();
@@ -1366,13 +1407,13 @@ public:
     // starks.cpp:255-296: q (NE x 3, column-major, ld NE) -> INTT -> split
     // into q_deg pieces -> NTT on the coset -> cm4 (n_cm4 x NE); the pieces
     // on the n domain too (cm4_n, for evmap)
-    int quotient_pieces(const uint64_t *q, uint64_t *cm4)
+    virtual int quotient_pieces()
     {
-        CK(zkgpu_gl_ntt_dev(qq1, NE, q, NE, NE, 3, 1));
+        CK(zkgpu_gl_ntt_dev(qq1, NE, S.sec[SEC_Q_2NS], NE, NE, 3, 1));
         CK(zkgpu_memset_dev(qq2, 0, (uint64_t)info.n_cm4 * NE * 8));
         uint64_t shift_in = pw(inv(7), N);
         CK(zkgpu_qsplit_dev(qq2, NE, qq1, NE, N, info.q_deg, shift_in));
-        CK(zkgpu_gl_ntt_dev(cm4, NE, qq2, NE, NE, info.n_cm4, 0));
+        CK(zkgpu_gl_ntt_dev(S.sec[SEC_CM4_2NS], NE, qq2, NE, NE, info.n_cm4, 0));
         if (lean()) return 0;  // evmap reads the pieces' extended rows
         // the quotient pieces on the n-domain too (for evmap below): qq2 holds
         // coset-scaled coefficients c_k 7^k (k < N, the rest zero); plain
