@@ -14,6 +14,12 @@
  *
  * Element type: Goldilocks u64, p = 2^64 - 2^32 + 1; inputs may be
  * non-canonical, outputs are canonical.  Extension elements are 3 u64.
+ * The layout changes and copies (zkgpu_rows_to_cols_dev, zkgpu_cols_to_rows_dev,
+ * zkgpu_copy_rows_dev, zkgpu_cols3_to_interleaved_dev) move words as they are.
+ *
+ * Leading dimensions: a column of a call over n rows needs ld >= n (the rows
+ * in [n, ld) are neither read nor written).  The stage primitives below
+ * return ZKGPU_ERR_ARG, with nothing queued, when an ld cannot hold the rows.
  *
  * Threading: one calling host thread per process/device (the reference calls
  * genProof from one thread, prover.cpp:182-255).  Kernels are enqueued on
@@ -89,7 +95,7 @@ int zkgpu_gl_extend_pol_dev(uint64_t *out, uint64_t ld_out, const uint64_t *in, 
  * (host/starks.cpp, the lean memory plan).  Same values as extendPol
  * (starks.cpp:53,134,215) out of place. */
 int zkgpu_gl_extend_pol_inplace_dev(uint64_t *base, uint64_t n_ext, uint64_t n, uint64_t ncols);
-/* row-major <-> column-major on device (boundary layout change) */
+/* row-major <-> column-major on device (boundary layout change); ld >= nrows */
 int zkgpu_rows_to_cols_dev(uint64_t *cols, uint64_t ld, const uint64_t *rows, uint64_t nrows, uint64_t ncols);
 int zkgpu_cols_to_rows_dev(uint64_t *rows, const uint64_t *cols, uint64_t ld, uint64_t nrows, uint64_t ncols);
 
@@ -279,7 +285,8 @@ typedef struct {
 } zkgpu_sections;
 
 /* Executor stand-in for synthetic traces: column cols[k] of a column-major
- * buffer gets the deterministic pseudo-random elements rand(seed, stream, col, row). */
+ * buffer gets the deterministic pseudo-random elements rand(seed, stream, col, row).
+ * ZKGPU_ERR_ARG when ncols > 65535 or nrows > ld. */
 int zkgpu_rand_cols_dev(uint64_t *base, uint64_t ld, const uint32_t *cols, uint32_t ncols, uint64_t nrows,
                         uint64_t seed, uint64_t stream);
 /* the same for a row block of a 2^log_n-row domain: local row r of the
@@ -358,7 +365,10 @@ int zkgpu_zxp_jit_source(const void *instr, uint32_t n_instr, const void *opnd, 
 
 /* Polinomial::calculateZ(z, num, den) (polinomial.hpp:586-607), F_p^3 columns
  * (3 consecutive columns of ld each).  *closes = 1 iff z[n-1]*num[n-1]/den[n-1] == 1
- * (the reference's zkassert). */
+ * (the reference's zkassert).  ZKGPU_ERR_ARG when z_ld, num_ld or den_ld < n
+ * (the block and batched forms alike).  A zero denominator is outside the
+ * contract (the reference inverts the whole column at once, this per thread:
+ * they differ there). */
 int zkgpu_calculate_z_dev(uint64_t *z, uint64_t z_ld, const uint64_t *num, uint64_t num_ld, const uint64_t *den,
                           uint64_t den_ld, uint64_t n, int *closes);
 /* One row block of the same grand product (the row-sharded prover: each rank
@@ -407,7 +417,7 @@ int zkgpu_xdivxsub_rows_dev(uint64_t *xdiv, uint64_t *xdivw, const uint64_t xi[3
 int zkgpu_lagrange_xi_rows_dev(uint64_t *lev, uint64_t *lpev, uint64_t ld, const uint64_t xi[3], uint32_t n_bits,
                                uint64_t row0, uint64_t nrows);
 
-/* base^k for k < n into 3 columns of ld (LEv / LpEv, starks.cpp:308-324) */
+/* base^k for k < n into 3 columns of ld >= n (LEv / LpEv, starks.cpp:308-324) */
 int zkgpu_ext_powers_dev(uint64_t *out, uint64_t ld, const uint64_t base[3], uint64_t n);
 
 /* cols[c][k] *= base^k for k < n, c < ncols (canonical outputs): the coset
@@ -416,7 +426,8 @@ int zkgpu_ext_powers_dev(uint64_t *out, uint64_t ld, const uint64_t base[3], uin
  * pieces between coset-scaled and plain coefficients. */
 int zkgpu_scale_by_powers_dev(uint64_t *cols, uint64_t ld, uint32_t ncols, uint64_t n, uint64_t base);
 
-/* quotient split (starks.cpp:266-281): qq2 col 3p+d row k = qq1 col d row pN+k * shift_in^p, k < n */
+/* quotient split (starks.cpp:266-281): qq2 col 3p+d row k = qq1 col d row pN+k * shift_in^p, k < n;
+ * ld2 >= n and ld1 >= q_deg * n (ZKGPU_ERR_ARG otherwise) */
 int zkgpu_qsplit_dev(uint64_t *qq2, uint64_t ld2, const uint64_t *qq1, uint64_t ld1, uint64_t n, uint32_t q_deg,
                      uint64_t shift_in);
 /* the same for dim input columns into output columns stride*p + d (d < dim
@@ -436,7 +447,7 @@ int zkgpu_qsplit_cols_dev(uint64_t *qq2, uint64_t ld2, const uint64_t *qq1, uint
 int zkgpu_h1h2_dev(uint64_t *h1, uint64_t h1_ld, uint64_t *h2, uint64_t h2_ld, const uint64_t *f, uint64_t f_ld,
                    const uint64_t *t, uint64_t t_ld, uint64_t n, uint32_t dim, uint64_t *missing_row);
 
-/* 3 ext columns (ld) -> interleaved n x 3 (the FRI polynomial layout, friProve.cpp) */
+/* 3 ext columns (ld >= n) -> interleaved n x 3 (the FRI polynomial layout, friProve.cpp) */
 int zkgpu_cols3_to_interleaved_dev(uint64_t *out, const uint64_t *cols, uint64_t ld, uint64_t n);
 
 /* MerkleTreeGL::getGroupProof for a row-major device source (FRI trees) */

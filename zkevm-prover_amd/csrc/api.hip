@@ -1012,7 +1012,8 @@ int zkgpu_rand_cols_dev(uint64_t *base, uint64_t ld, const uint32_t *cols, uint3
 {
     int rc;
     if ((rc = require_init())) return rc;
-    if (!ncols) return 0;
+    if (!ncols || !nrows) return 0;
+    if (ncols > 65535 || nrows > ld) return set_error(ZKGPU_ERR_ARG, "rand_cols: bad shape");
     char *p = param_buf(ncols * 4);
     if (!p) return set_error(ZKGPU_ERR_OOM, "param buffer");
     if ((rc = check_hip(hipMemcpyAsync(p, cols, ncols * 4, hipMemcpyHostToDevice, g_ctx.stream), "H2D"))) return rc;
@@ -1180,6 +1181,7 @@ int zkgpu_calculate_z_block_dev(uint64_t *z, uint64_t z_ld, const uint64_t *num,
         for (int k = 0; k < 3; k++) total[k] = z0[k] % HP;
         return 0;
     }
+    if (z_ld < n || num_ld < n || den_ld < n) return set_error(ZKGPU_ERR_ARG, "calculate_z: ld < n");
     const size_t words = calculate_z_scratch_words(n);
     uint64_t *scr = workspace(2, (words + 8) * sizeof(uint64_t));
     if (!scr) return ZKGPU_ERR_OOM;
@@ -1199,6 +1201,9 @@ int zkgpu_calculate_z_many_dev(const zkgpu_z_req *req, uint32_t nz, uint64_t n, 
         for (uint32_t k = 0; k < nz; k++) closes[k] = 1;  // an empty product
         return 0;
     }
+    for (uint32_t k = 0; k < nz; k++)
+        if (req[k].z_ld < n || req[k].num_ld < n || req[k].den_ld < n)
+            return set_error(ZKGPU_ERR_ARG, "calculate_z_many: request %u: ld < n", k);
     // the requests run in stream order on one scratch; each keeps its total
     const size_t words = calculate_z_scratch_words(n);
     uint64_t *scr = workspace(2, (words + 3ULL * nz + 8) * sizeof(uint64_t));
@@ -1360,6 +1365,7 @@ int zkgpu_ext_powers_dev(uint64_t *out, uint64_t ld, const uint64_t base[3], uin
     int rc;
     if ((rc = require_init())) return rc;
     if (!n) return 0;
+    if (ld < n) return set_error(ZKGPU_ERR_ARG, "ext_powers: ld < n");
     return ext_powers(out, ld, base, n, g_ctx.stream);
 }
 
@@ -1378,6 +1384,7 @@ int zkgpu_qsplit_dev(uint64_t *qq2, uint64_t ld2, const uint64_t *qq1, uint64_t 
     int rc;
     if ((rc = require_init())) return rc;
     if (!n) return 0;
+    if (ld2 < n || ld1 / n < q_deg) return set_error(ZKGPU_ERR_ARG, "qsplit: ld2 < n or ld1 < q_deg * n");
     return qsplit(qq2, ld2, qq1, ld1, n, q_deg, shift_in, 3, 3, g_ctx.stream);
 }
 
@@ -1388,6 +1395,7 @@ int zkgpu_qsplit_cols_dev(uint64_t *qq2, uint64_t ld2, const uint64_t *qq1, uint
     if ((rc = require_init())) return rc;
     if (!n || !dim) return 0;
     if (dim > stride) return set_error(ZKGPU_ERR_ARG, "qsplit_cols: dim %u > stride %u", dim, stride);
+    if (ld2 < n || ld1 / n < q_deg) return set_error(ZKGPU_ERR_ARG, "qsplit_cols: ld2 < n or ld1 < q_deg * n");
     return qsplit(qq2, ld2, qq1, ld1, n, q_deg, shift_in, dim, stride, g_ctx.stream);
 }
 
@@ -1465,6 +1473,7 @@ int zkgpu_cols3_to_interleaved_dev(uint64_t *out, const uint64_t *cols, uint64_t
     int rc;
     if ((rc = require_init())) return rc;
     if (!n) return 0;
+    if (ld < n) return set_error(ZKGPU_ERR_ARG, "cols3_to_interleaved: ld < n");
     return cols3_to_interleaved(out, cols, ld, n, g_ctx.stream);
 }
 

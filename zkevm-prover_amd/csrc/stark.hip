@@ -284,11 +284,11 @@ __global__ void __launch_bounds__(ZXP_THREADS) k_zxp_eval(ZxpEnv e)
 
 // ---------------------------------------------------------------- calculateZ
 // Z[k] = prod_{i<k} num[i] / den[i]  (starks.cpp:146-224, polinomial.hpp:560-607).
-// Tiles of Z_TILE = 256 x 8 rows.  Global traffic is always row-coalesced (lane
+// Tiles of Z_TILE = 256 x 4 rows.  Global traffic is always row-coalesced (lane
 // = consecutive row); the per-thread CONTIGUOUS runs a prefix product needs are
 // read from an LDS image of the tile.
 //   k_z_ratio:  ratio = num / den (Montgomery batch inversion over each
-//               thread's 8 strided rows), LDS image, per-thread run products,
+//               thread's 4 strided rows), LDS image, per-thread run products,
 //               block scan -> per-thread exclusive prefixes + tile total
 //   k_z_totals: exclusive prefix of the tile totals (one workgroup)
 //   k_z_apply:  z = tile prefix * thread prefix * running product, through LDS

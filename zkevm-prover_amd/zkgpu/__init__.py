@@ -417,6 +417,39 @@ def cols_to_rows_dev(rows, cols, ld, nrows, ncols):
     _check(lib().zkgpu_cols_to_rows_dev(_addr(rows), _addr(cols), ld, nrows, ncols), "zkgpu_cols_to_rows_dev")
 
 
+def _u32s(cols):
+    """host uint32 array of a column list (None stays None: the identity)"""
+    return None if cols is None else np.ascontiguousarray(cols, dtype=np.uint32)
+
+
+def rand_cols_dev(base, ld, cols, nrows, seed, stream):
+    """base[c * ld + r] = rand_u64(seed, stream, c, r) (zkgpu.synthetic) for the
+    listed columns c, r < nrows"""
+    c = _u32s(cols)
+    _check(lib().zkgpu_rand_cols_dev(_addr(base), ld, c.ctypes.data, c.size, nrows, seed, stream),
+           "zkgpu_rand_cols_dev")
+
+
+def rand_cols_rows_dev(base, ld, cols, row0, nrows, log_n, seed, stream):
+    """the same for a row block: local row r holds global row (row0 + r) mod 2^log_n"""
+    c = _u32s(cols)
+    _check(lib().zkgpu_rand_cols_rows_dev(_addr(base), ld, c.ctypes.data, c.size, row0, nrows, log_n, seed, stream),
+           "zkgpu_rand_cols_rows_dev")
+
+
+def copy_rows_dev(dst, dst_ld, dst_row0, dst_cols, src, src_ld, src_row0, src_log_mod, src_cols, ncols, nrows):
+    """dst column dst_cols[k] (k if None), rows dst_row0 + j  <-  src column
+    src_cols[k] (k if None), rows src_row0 + j (mod 2^src_log_mod if non-zero), j < nrows"""
+    dc, sc = _u32s(dst_cols), _u32s(src_cols)
+    _check(lib().zkgpu_copy_rows_dev(_addr(dst), dst_ld, dst_row0, _addr(dc), _addr(src), src_ld, src_row0,
+                                     src_log_mod, _addr(sc), ncols, nrows), "zkgpu_copy_rows_dev")
+
+
+def cols3_to_interleaved_dev(out, cols, ld, n):
+    """out[3 k + c] = cols[c * ld + k], k < n, c < 3 (words copied as they are)"""
+    _check(lib().zkgpu_cols3_to_interleaved_dev(_addr(out), _addr(cols), ld, n), "zkgpu_cols3_to_interleaved_dev")
+
+
 def poseidon_batch_dev(out, src, n, full=True):
     _check(lib().zkgpu_gl_poseidon_batch_dev(_addr(out), _addr(src), n, int(full)), "zkgpu_gl_poseidon_batch_dev")
 
