@@ -313,6 +313,17 @@ int zkgpu_copy_rows_dev(uint64_t *dst, uint64_t dst_ld, uint64_t dst_row0, const
 int zkgpu_gather_rows_dev(uint64_t *out, const uint64_t *src, uint64_t ld, uint32_t ncols, const uint64_t *rows,
                           uint64_t nrows);
 
+/* The rows of a column-major section that are not zero (the prover's constraint check,
+ * include/zkgpu_stark.h zkgpu_stark_check_*).
+ * out (device, 1 + max_rows words): out[0] = number of rows i < n with cols[c*ld + i] != 0 (mod p) for
+ * some c < ncols; out[1 + k] = the k-th lowest such row, ascending, UINT64_MAX past the last.
+ * Inputs may be non-canonical (p and 0 are both zero).  Enqueued on the library stream, no host
+ * synchronisation.  ZKGPU_ERR_ARG: ld < n, max_rows > 4096, null pointers; n = 0 or ncols = 0 write count 0.
+ * The result does not depend on the launch geometry: per 1024-row block counts, then one workgroup
+ * that scans them and re-reads only the blocks holding the lowest max_rows hits. */
+int zkgpu_nonzero_rows_dev(uint64_t *out, const uint64_t *cols, uint64_t ld, uint32_t ncols,
+                           uint64_t n, uint32_t max_rows);
+
 /* Steps::step*_parser_first (steps.hpp:21-58; used at starks.cpp:73,155,193,
  * 241,371): evaluate one expression program (include/zkgpu_zxp.h) over every
  * row of its domain (2^log_dom rows).  instr/opnd are host arrays (uploaded),
@@ -350,6 +361,21 @@ int zkgpu_zxp_eval_block_dev(const void *instr, uint32_t n_instr, const void *op
 int zkgpu_zxp_compile(const void *instr, uint32_t n_instr, const void *opnd, uint32_t n_opnd, uint32_t n_tmp1,
                       uint32_t n_tmp3, const uint64_t *challenges, const uint64_t *publics, uint32_t n_publics,
                       const uint64_t *evals, uint32_t n_evals, uint32_t max_terms, zxp_compiled *out);
+
+/* A quotient program (step42ns) re-targeted to the trace domain (csrc/zxp_n_domain.cpp): the
+ * combination C it forms before its final "x ZI" is zero on every row of <omega_n> exactly when the
+ * trace satisfies every identity (with overwhelming probability over the combination challenge).
+ * Reads of SEC_CM1/CM2/CM3/CONST_2NS become reads of the matching _N section, their row shift (a
+ * multiple of 2^extend_bits, either sign) divided by 2^extend_bits (next = 2^extendBits -> 1,
+ * steps.hpp); SEC_Q_2NS stays, destination only, shift 0 (the caller points that section-table
+ * entry at n-row storage); ZXP_ZI becomes ZXP_LIT 1 and is accepted only as a factor of a ZXP_MUL
+ * stored to a SEC_Q_2NS column, of which there must be one; X, TMP1/3, LIT, CHAL, PUB are unchanged;
+ * everything else (EVAL, XDIV, XDIVW, any other section, a read of SEC_Q_2NS, unknown kinds,
+ * indices out of range) is ZKGPU_ERR_ARG with a message naming the operand or instruction.  Then
+ * evaluate with zkgpu_zxp_eval_dev at log_dom = n_bits, x_start = 1, extend_bits = 0.
+ * opnd_out: n_opnd operands; the instruction list is unchanged.  No GPU needed. */
+int zkgpu_zxp_to_n_domain(zxp_operand *opnd_out, const zxp_instr *instr, uint32_t n_instr,
+                          const zxp_operand *opnd, uint32_t n_opnd, uint32_t extend_bits);
 
 /* Diagnostics for the run-time compiled expression kernels (csrc/zxp_jit.hip):
  * compile a program exactly as zkgpu_zxp_eval_dev does and write the

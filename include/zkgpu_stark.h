@@ -195,6 +195,48 @@ int zkgpu_stark_probe_set(void *handle, const uint64_t *rows_n, uint32_t n_rows_
 int zkgpu_stark_probe_size(void *handle, uint32_t *n_recs, uint64_t *n_words);
 int zkgpu_stark_probe_read(void *handle, zkgpu_probe_rec *recs, uint32_t max_recs, uint64_t *payload, uint64_t max_words);
 
+/* ---- constraint check: the trace rows that break the AIR, before stage 4 ------
+ * A trace row that breaks a polynomial identity goes through a proof silently:
+ * stage 4 divides whatever step42ns computes by Z_H on the coset and the proof
+ * that comes out verifies nowhere.  With the check on, prove / prove_from_rows
+ * evaluate, between the last stage-3 program and stage 3's commit, the
+ * constraint combination C that step42ns forms before its final "x ZI" on the
+ * n domain itself (the program rewritten once by zkgpu_zxp_to_n_domain,
+ * include/zkgpu.h; its output borrows the head of q, nothing is added to a
+ * memory plan), and reduce it to the rows where C != 0
+ * (zkgpu_nonzero_rows_dev).  C vanishes on every row iff every identity holds
+ * there, with overwhelming probability over the combination challenge.  The
+ * check names ROWS, not constraints.
+ *
+ * The combination challenge: the transcript's challenge 4 is drawn from root 3,
+ * which does not exist yet, so the check uses the getField of a COPY of the
+ * transcript taken after challenges 2 and 3 (returned in `alpha`); the proof's
+ * transcript is untouched and a checked proof is the unchecked one bit for bit.
+ *
+ *   OFF     a proof queues exactly what it queued before.
+ *   REPORT  no host synchronisation is added inside the proof; the result is
+ *           read back after it, and prove returns what it would have returned.
+ *   STOP    one synchronisation at the check; with n_bad > 0 prove fails there
+ *           with a message naming the domain size, n_bad and the first failing
+ *           row, nothing of stage 3's commit or later is queued, and the prover
+ *           is left as after any other failed proof (under the lean plan the
+ *           trace has not been consumed).
+ * Timer line ZKGPU_CHECK_CONSTRAINTS, present only when the check ran.
+ * check_set rewrites the instance's step42ns once; a program the rewrite refuses
+ * makes it fail with that message and leaves the check off.  Refused: a sharded
+ * prover, an unknown mode.  Holds for every later proof until changed. */
+enum { ZKGPU_CHECK_OFF = 0, ZKGPU_CHECK_REPORT = 1, ZKGPU_CHECK_STOP = 2 };
+#define ZKGPU_CHECK_MAX_ROWS 16
+typedef struct {
+    uint32_t ran;                         /* 1: the last prove reached the check */
+    uint64_t n_bad;                       /* rows of the n domain where C != 0 */
+    uint64_t rows[ZKGPU_CHECK_MAX_ROWS];  /* the lowest of them, ascending; UINT64_MAX past the last */
+    uint64_t value[3];                    /* C at rows[0], canonical (0 when n_bad = 0) */
+    uint64_t alpha[3];                    /* the combination challenge used (above) */
+} zkgpu_check_result;
+int zkgpu_stark_check_set(void *handle, uint32_t mode);
+int zkgpu_stark_check_result(void *handle, zkgpu_check_result *out);
+
 /* ---- the Fiat-Shamir transcript the prover runs on the host, as the
  * reference's class Transcript (transcript.hpp:14-37, transcript.cpp:4-88):
  * Poseidon-GL sponge, 8-element rate, 4-element capacity.  Host code only

@@ -1108,7 +1108,9 @@ static int zxp_eval_run(const ZxpArgs &a)
         // interpreter records, no upload or stream sync here, so the host
         // prepares them while earlier work still runs on the stream
         ZxpJitIn J = zxp_jit_in(P.prog, a.sections, a.challenges, a.publics, a.evals);
-        if (!(J.zh_dev = zh_table(a.log_omega, a.extend_bits, P.zhinv, P.n_zhinv))) return -1;
+        // (the cached table is the real one: only a program that reads it asks for it)
+        J.zh_dev = nullptr;
+        if (P.uses_zi && !(J.zh_dev = zh_table(a.log_omega, a.extend_bits, P.zhinv, P.n_zhinv))) return -1;
         J.log_dom = a.log_dom;
         J.log_omega = a.log_omega;
         J.wrap = a.wrap ? 1u : 0u;

@@ -126,6 +126,114 @@ __global__ void k_gather_rows(uint64_t *out, const uint64_t *src, uint64_t ld, u
     }
 }
 
+// ---------------------------------------------------------------- nonzero rows
+// The rows of a column-major section that are not zero mod p, lowest first
+// (the prover's constraint check: the constraint combination on the trace
+// domain).  A streaming read: a wave takes 64 consecutive rows of one column
+// per load, the hits of a wave are the bits of its 64-bit ballot.  The result
+// does not depend on the launch geometry or on the order the workgroups
+// finish in: k_nz_count writes one count per block of NZ_BLOCK rows (block b
+// is rows [b NZ_BLOCK, (b + 1) NZ_BLOCK) whatever the grid), then ONE
+// workgroup (k_nz_emit) scans the counts, writes the total and re-reads only
+// the blocks that hold the lowest max_rows hits; a hit's place in the output
+// is its block's exclusive prefix plus its rank inside the block.
+constexpr uint32_t NZ_THREADS = 256;     // 4 waves
+constexpr uint32_t NZ_BLOCK = 1024;      // rows per counted block: wave w takes rows [256 w, 256 w + 256) of it
+constexpr uint32_t NZ_MAX_ROWS = 4096;   // k_nz_emit's block list lives in LDS
+
+// the lanes whose row, of the 64 consecutive rows from r0, is not zero in some
+// column (rows >= n are not read).  Non-canonical words: 0 and p are zero.
+__device__ __forceinline__ uint64_t nz_ballot(const uint64_t *cols, uint64_t ld, uint32_t ncols, uint64_t n,
+                                              uint64_t r0)
+{
+    const uint64_t r = r0 + (threadIdx.x & 63);
+    bool f = false;
+    if (r < n)
+        for (uint32_t c = 0; c < ncols; c++) {
+            const uint64_t v = cols[(uint64_t)c * ld + r];
+            f |= v != 0 && v != ZK_P;
+        }
+    return __ballot(f);
+}
+
+__global__ __launch_bounds__(NZ_THREADS) void k_nz_count(uint32_t *counts, const uint64_t *cols, uint64_t ld,
+                                                         uint32_t ncols, uint64_t n)
+{
+    __shared__ uint32_t wsum[NZ_THREADS / 64];
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint64_t base = (uint64_t)blockIdx.x * NZ_BLOCK + wave * 256;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < 4; s++) cnt += (uint32_t)__popcll(nz_ballot(cols, ld, ncols, n, base + 64 * s));
+    if ((threadIdx.x & 63) == 0) wsum[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// one workgroup.  out[0] = the total, out[1 + k] = the k-th lowest hit (k <
+// max_rows <= NZ_MAX_ROWS), UINT64_MAX past the last
+__global__ __launch_bounds__(NZ_THREADS) void k_nz_emit(uint64_t *out, const uint32_t *counts, uint32_t nblocks,
+                                                        const uint64_t *cols, uint64_t ld, uint32_t ncols, uint64_t n,
+                                                        uint32_t max_rows)
+{
+    __shared__ uint64_t part[NZ_THREADS];
+    // the blocks with a hit among the lowest max_rows: each holds at least one
+    // and starts below max_rows, so there are at most max_rows of them
+    __shared__ uint32_t list_blk[NZ_MAX_ROWS], list_pre[NZ_MAX_ROWS];
+    __shared__ uint32_t n_list;
+    __shared__ uint32_t wsum[NZ_THREADS / 64];
+    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    // thread t scans blocks [b0, b1)
+    const uint32_t chunk = (nblocks + NZ_THREADS - 1) / NZ_THREADS;
+    const uint32_t b0 = min(t * chunk, nblocks), b1 = min(b0 + chunk, nblocks);
+    uint64_t sum = 0;
+    for (uint32_t b = b0; b < b1; b++) sum += counts[b];
+    part[t] = sum;
+    if (t == 0) n_list = 0;
+    __syncthreads();
+    uint64_t pre = 0, total = 0;
+    for (uint32_t k = 0; k < NZ_THREADS; k++) {
+        const uint64_t v = part[k];
+        pre += k < t ? v : 0;
+        total += v;
+    }
+    if (t == 0) out[0] = total;
+    for (uint64_t k = (total < max_rows ? total : max_rows) + t; k < max_rows; k += NZ_THREADS) out[1 + k] = UINT64_MAX;
+    // (the list's order does not matter: an entry carries its own prefix)
+    for (uint32_t b = b0; b < b1 && pre < max_rows; b++) {
+        const uint32_t c = counts[b];
+        if (c) {
+            const uint32_t slot = atomicAdd(&n_list, 1u);
+            list_blk[slot] = b;
+            list_pre[slot] = (uint32_t)pre;
+        }
+        pre += c;
+    }
+    __syncthreads();
+    const uint32_t nl = n_list;
+    for (uint32_t e = 0; e < nl; e++) {
+        const uint64_t base = (uint64_t)list_blk[e] * NZ_BLOCK + wave * 256;
+        uint64_t bal[4];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (uint32_t s = 0; s < 4; s++) {
+            bal[s] = nz_ballot(cols, ld, ncols, n, base + 64 * s);
+            cnt += (uint32_t)__popcll(bal[s]);
+        }
+        if (lane == 0) wsum[wave] = cnt;
+        __syncthreads();
+        uint32_t rank = list_pre[e];
+        for (uint32_t w = 0; w < wave; w++) rank += wsum[w];
+#pragma unroll
+        for (uint32_t s = 0; s < 4; s++) {
+            const uint32_t k = rank + (uint32_t)__popcll(bal[s] & ((1ULL << lane) - 1));
+            if (((bal[s] >> lane) & 1) && k < max_rows) out[1 + (uint64_t)k] = base + 64 * s + lane;
+            rank += (uint32_t)__popcll(bal[s]);
+        }
+        __syncthreads();
+    }
+}
+
 // ---------------------------------------------------------------- ZXP interpreter
 struct ZxpEnv {
     const ZOp *prog;
@@ -700,6 +808,22 @@ static int gather_rows(uint64_t *out, const uint64_t *src, uint64_t ld, uint32_t
     return check_launch("k_gather_rows");
 }
 
+// counts: nblk(n, NZ_BLOCK) words of device scratch
+static int nonzero_rows(uint64_t *out, uint32_t *counts, const uint64_t *cols, uint64_t ld, uint32_t ncols, uint64_t n,
+                        uint32_t max_rows, hipStream_t s)
+{
+    const uint32_t nblocks = nblk(n, NZ_BLOCK);
+    if (nblocks) {
+        prof_begin(s);
+        hipLaunchKernelGGL(k_nz_count, dim3(nblocks), dim3(NZ_THREADS), 0, s, counts, cols, ld, ncols, n);
+        prof_end("k_nz_count", 8.0 * (double)ncols * (double)n + 4.0 * nblocks, s);
+    }
+    prof_begin(s);
+    hipLaunchKernelGGL(k_nz_emit, dim3(1), dim3(NZ_THREADS), 0, s, out, counts, nblocks, cols, ld, ncols, n, max_rows);
+    prof_end("k_nz_emit", 4.0 * nblocks + 8.0 * (1 + max_rows), s);
+    return check_launch("k_nz_emit");
+}
+
 int zxp_eval(const ZxpLaunch &L, hipStream_t s)
 {
     Ctx &c = ctx();
@@ -860,4 +984,22 @@ extern "C" int zkgpu_gather_rows_dev(uint64_t *out, const uint64_t *src, uint64_
     if (!out || !src || !rows) return zk::set_error(ZKGPU_ERR_ARG, "gather_rows: null pointer");
     if (nrows > UINT64_MAX / ncols) return zk::set_error(ZKGPU_ERR_ARG, "gather_rows: nrows x ncols overflows");
     return zk::gather_rows(out, src, ld, ncols, rows, nrows, zk::ctx().stream);
+}
+
+// the C-ABI of the nonzero-row reduction (include/zkgpu.h), beside its kernels
+extern "C" int zkgpu_nonzero_rows_dev(uint64_t *out, const uint64_t *cols, uint64_t ld, uint32_t ncols, uint64_t n,
+                                      uint32_t max_rows)
+{
+    if (!zk::ctx().ready) return zk::set_error(ZKGPU_ERR_INIT, "zkgpu_init() not called");
+    if (!out) return zk::set_error(ZKGPU_ERR_ARG, "nonzero_rows: null pointer");
+    if (max_rows > zk::NZ_MAX_ROWS)
+        return zk::set_error(ZKGPU_ERR_ARG, "nonzero_rows: max_rows %u > %u", max_rows, zk::NZ_MAX_ROWS);
+    if (!ncols) n = 0;  // no column: no row is nonzero
+    if (n && !cols) return zk::set_error(ZKGPU_ERR_ARG, "nonzero_rows: null pointer");
+    if (ld < n) return zk::set_error(ZKGPU_ERR_ARG, "nonzero_rows: ld < n");
+    if (n > (1ULL << 32)) return zk::set_error(ZKGPU_ERR_ARG, "nonzero_rows: more than 2^32 rows");
+    uint32_t *counts = nullptr;
+    if (n && !(counts = (uint32_t *)zk::workspace(7, ((n + zk::NZ_BLOCK - 1) / zk::NZ_BLOCK) * sizeof(uint32_t))))
+        return ZKGPU_ERR_OOM;
+    return zk::nonzero_rows(out, counts, cols, ld, ncols, n, max_rows, zk::ctx().stream);
 }

@@ -37,7 +37,8 @@ struct Ctx {
     uint64_t *post_lo = nullptr;
     uint64_t *post_hi = nullptr;
     // scratch workspaces
-    Workspace ws[7];  // 0-3 NTT / staging, 4 H1H2 scratch, 5 rocPRIM temp, 6 ZXP segment carries
+    Workspace ws[8];  // 0-3 NTT / staging, 4 H1H2 scratch, 5 rocPRIM temp, 6 ZXP segment carries,
+                      // 7 nonzero-rows block counts
     // Poseidon constants on device
     uint64_t *poseidon_rc = nullptr;
 };

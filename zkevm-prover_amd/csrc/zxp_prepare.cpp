@@ -157,13 +157,17 @@ int zxp_plan(const ZxpArgs &a, ZxpPlan &p)
     if ((rc = check_program(p.prog))) return rc;
     p.n_dot_terms = 0;
     for (uint32_t t = 0; t < p.prog.n_term; t++) p.n_dot_terms += p.prog.term[t].src != ZXP_TERM_ONE;
-    // zhInv[j] = 1/(7^N * W[eb]^j - 1)  (zhInv.cpp:7-31), N = 2^(log_omega - eb)
+    // zhInv[j] = 1/(7^N * W[eb]^j - 1)  (zhInv.cpp:7-31), N = 2^(log_omega - eb); only for a program
+    // with a ZI operand (on a domain where Z_H vanishes -- the trace domain, x_start 1 -- it has no
+    // inverse, and no program without ZI reads the table: it stays zero)
     p.n_zhinv = 1u << a.extend_bits;
+    p.uses_zi = false;
+    for (uint32_t k = 0; k < a.n_opnd; k++) p.uses_zi |= a.opnd[k].kind == ZXP_ZI;
     const uint64_t sn = h_pow(7, 1ULL << (a.log_omega - a.extend_bits)), we = h_w(a.extend_bits);
     uint64_t w = 1;
     for (uint32_t j = 0; j < p.n_zhinv; j++) {
         const uint64_t x = h_mul(sn, w);  // < HP
-        p.zhinv[j] = h_inv(x ? x - 1 : HP - 1);
+        p.zhinv[j] = p.uses_zi ? h_inv(x ? x - 1 : HP - 1) : 0;
         w = h_mul(w, we);
     }
     p.bytes = 0;

@@ -83,6 +83,7 @@ struct ZxpPlan {
     uint32_t n_dot_terms;  // DOT terms with a source: the interpreter's ZTerm records
     uint64_t zhinv[64];    // zhInv[j] = 1/(7^N * W[eb]^j - 1), j < n_zhinv (zhInv.cpp:7-31)
     uint32_t n_zhinv;
+    bool uses_zi;  // the program has a ZI operand: else zhinv is zero and nothing reads it
     double bytes;  // algorithmic bytes: every distinct column operand read once per row + written columns
     bool jit;      // the run-time compiled kernels (csrc/zxp_jit.hip), else the interpreter
 };

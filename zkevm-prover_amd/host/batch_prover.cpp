@@ -22,10 +22,14 @@
 // step52ns), run as GPU programs (ProverInfo, host/stark_info.cpp); for the
 // zkEVM's parser bytecode, StepsGPU (host/zkgpu_steps.hpp) is the binding.
 //
-// Usage: zkgpu_batch_prover [--stream-trace] [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]]
+// Usage: zkgpu_batch_prover [--stream-trace] [--check-trace] [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]]
 //                           <config.json>
 //        (--stream-trace: the trace file's rows stay in host memory and cross
 //        PCIe under stage 1 of the proof, zkgpu_stark_prove_from_rows; single GPU)
+//        (--check-trace: the constraint check in its STOP mode, zkgpu_stark_check_set:
+//        a trace with a row that breaks the AIR ends the run before stage 3's
+//        commit with the first such row in the message, a non-zero status and
+//        no proof files; single GPU)
 //        (--shard: one rank of ONE proof row-sharded over WORLD processes,
 //        zkgpu_stark_create_sharded; every rank runs this command with the
 //        same config, rank 0 writes the outputs.  rccl: rank 0 writes the
@@ -133,6 +137,7 @@ struct Shard {
     std::string comm;  // "" (single GPU), "rccl:<file>", "host:<name>"
     int device = -1;
     bool stream_trace = false;  // --stream-trace: zkgpu_stark_prove_from_rows instead of set_cm1 + prove
+    bool check_trace = false;   // --check-trace: zkgpu_stark_check_set(ZKGPU_CHECK_STOP)
 };
 
 // The RCCL id through a file: rank 0 writes it (atomic rename), the others
@@ -254,6 +259,8 @@ static int prove(const std::string &config_path, const Shard &sh)
         for (int i = 0; i < 4; i++) root[i] = vk["constRoot"][i].u64();
         check_root("zkevmVerkey", root, verkey);
     }
+    if (sh.check_trace && zkgpu_stark_check_set(h, ZKGPU_CHECK_STOP))
+        throw std::runtime_error(std::string("--check-trace: ") + zkgpu_stark_last_error());
     const auto t1 = clk::now();
     const uint64_t len = zkgpu_stark_proof_len(h);
     if (len != flat_len(info)) throw std::runtime_error("proof length mismatch");
@@ -294,6 +301,11 @@ int main(int argc, char **argv)
                 a += 1;
                 continue;
             }
+            if (opt == "--check-trace") {
+                sh.check_trace = true;
+                a += 1;
+                continue;
+            }
             if (opt == "--shard") {
                 unsigned r = 0, w = 0;
                 if (sscanf(argv[a + 1], "%u/%u", &r, &w) != 2 || !w || r >= w)
@@ -313,9 +325,11 @@ int main(int argc, char **argv)
             throw std::runtime_error("--shard with WORLD > 1 needs --comm");
         if (sh.stream_trace && !sh.comm.empty())
             throw std::runtime_error("--stream-trace is for the single-GPU prover (no --comm)");
+        if (sh.check_trace && sh.world > 1)
+            throw std::runtime_error("--check-trace is for the single-GPU prover (not with --shard at WORLD > 1)");
         if (argc == a + 1 && argv[a][0] != '-') return prove(argv[a], sh);
         fprintf(stderr,
-                "usage: %s [--stream-trace] [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] "
+                "usage: %s [--stream-trace] [--check-trace] [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] "
                 "<config.json>\n"
                 "       %s --info <starkinfo.json>\n"
                 "       %s --zkin <starkinfo.json> <flat proof> <publics.json> <outdir>\n",

@@ -729,6 +729,11 @@ public:
     {
         return fail("stark (sharded): probe_set is single-GPU only (the sampled rows live on other ranks)");
     }
+    int check_set(uint32_t) override
+    {
+        return fail("stark (sharded): check_set is single-GPU only (the n-domain sections live in row blocks on the "
+                    "ranks)");
+    }
     int prove_from_rows(const uint64_t *, int, uint64_t *) override
     {
         return fail("stark (sharded): prove_from_rows is single-GPU only (each rank loads its rows: set_cm1 / "

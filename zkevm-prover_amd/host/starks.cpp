@@ -221,6 +221,7 @@ public:
         if (lowered_lde_batch) zkgpu_set_lde_batch_cols(0);
         for (void *t : cm1_ticket) (void)zkgpu_load_wait(t);
         probe_clear();
+        if (check_dev) (void)zkgpu_dev_free(check_dev);
         for (void *p : allocs) zkgpu_dev_free(p);
     }
 
@@ -1171,6 +1172,113 @@ public:
         return 0;
     }
 
+    // ---- constraint check (include/zkgpu_stark.h zkgpu_stark_check_*): the
+    // quotient program on the trace domain, before stage 3's commit.  The
+    // combination C that step42ns forms before its "x ZI" is zero on every
+    // row of <omega_n> iff the trace satisfies every identity, so the same
+    // instruction list over the n-domain sections (check_opnd: step42ns's
+    // operands rewritten by zkgpu_zxp_to_n_domain) names the rows that break
+    // the AIR at 1 / 2^blowup of the quotient's rows.  Its 3 output columns
+    // borrow the head of q (dead until stage 4); the rows that are not zero
+    // come from zkgpu_nonzero_rows_dev into a 20-word device block of the
+    // check's own (outside the memory plan, as the probe's).
+    uint32_t check_mode = ZKGPU_CHECK_OFF;
+    std::vector<zxp_operand> check_opnd;
+    uint64_t *check_dev = nullptr;  // [0] n_bad, [1, 17) rows, [17, 20) C at the first
+    bool check_pending = false;     // REPORT: the block is read back after the proof
+    zkgpu_check_result check_res = {};
+
+    virtual int check_set(uint32_t mode)
+    {
+        if (mode > ZKGPU_CHECK_STOP) return fail("check_set: unknown mode %u", mode);
+        if (mode == ZKGPU_CHECK_OFF) {
+            check_mode = ZKGPU_CHECK_OFF;
+            return 0;
+        }
+        if (check_opnd.empty()) {
+            std::vector<zxp_operand> o(step42ns.opnd.size() + 1);
+            if (zkgpu_zxp_to_n_domain(o.data(), step42ns.instr.data(), (uint32_t)step42ns.instr.size(),
+                                      step42ns.opnd.data(), (uint32_t)step42ns.opnd.size(), eb)) {
+                check_mode = ZKGPU_CHECK_OFF;
+                return fail("check_set: step42ns: %s; the check is off", zkgpu_last_error());
+            }
+            o.resize(step42ns.opnd.size());
+            check_opnd.swap(o);
+        }
+        if (!check_dev) {
+            void *v = nullptr;
+            if (zkgpu_dev_malloc(&v, (4 + ZKGPU_CHECK_MAX_ROWS) * 8)) {
+                check_mode = ZKGPU_CHECK_OFF;
+                return fail("check_set: %s; the check is off", zkgpu_last_error());
+            }
+            check_dev = (uint64_t *)v;
+        }
+        check_mode = mode;
+        return 0;
+    }
+
+    // between the last stage-3 program and stage 3's commit: every n-domain
+    // section is alive under both memory plans.  The combination challenge
+    // (challenge 4) comes from root 3, which does not exist yet, so the check
+    // takes its own: the getField of a COPY of the transcript as it stands
+    // (challenges 2 and 3 drawn); the proof's transcript is not touched.
+    int check_run(const Transcript &tr, const uint64_t ch[24])
+    {
+        tstart();
+        Transcript fork = tr;
+        uint64_t chk[24];
+        memcpy(chk, ch, sizeof chk);
+        fork.get_field(chk + 12);
+        memcpy(check_res.alpha, chk + 12, 24);
+        zkgpu_sections T = S;
+        const uint32_t pairs[4][2] = {{SEC_CM1_2NS, SEC_CM1_N}, {SEC_CM2_2NS, SEC_CM2_N}, {SEC_CM3_2NS, SEC_CM3_N},
+                                      {SEC_CONST_2NS, SEC_CONST_N}};
+        for (const auto &p : pairs) {
+            T.sec[p[0]] = S.sec[p[1]];
+            T.ld[p[0]] = N;
+            T.ncols[p[0]] = S.ncols[p[1]];
+        }
+        uint64_t *c = S.sec[SEC_Q_2NS];  // its first 3 N words, ld N
+        T.ld[SEC_Q_2NS] = N;
+        const uint64_t ev0[3] = {0, 0, 0};
+        CK(zkgpu_zxp_eval_dev(step42ns.instr.data(), (uint32_t)step42ns.instr.size(), check_opnd.data(),
+                              (uint32_t)check_opnd.size(), step42ns.n_tmp1 ? step42ns.n_tmp1 : 1,
+                              step42ns.n_tmp3 ? step42ns.n_tmp3 : 1, &T, info.n_bits, chk, publics.data(),
+                              (uint32_t)publics.size(), ev0, 0, nullptr, nullptr, 0, 1));
+        CK(zkgpu_nonzero_rows_dev(check_dev, c, N, 3, N, ZKGPU_CHECK_MAX_ROWS));
+        // C at the first failing row (a row index past the domain -- none failed -- reads 0)
+        CK(zkgpu_gather_rows_dev(check_dev + 1 + ZKGPU_CHECK_MAX_ROWS, c, N, 3, check_dev + 1, 1));
+        if (tstop("ZKGPU_CHECK_CONSTRAINTS")) return -1;
+        if (check_mode == ZKGPU_CHECK_REPORT) {
+            check_pending = true;
+            return 0;
+        }
+        if (check_readback()) return -1;  // STOP: the one synchronisation
+        if (check_res.n_bad)
+            return fail("constraint check: %llu of the 2^%u = %llu rows of the trace break the AIR; the first is row "
+                        "%llu (zkgpu_stark_check_result lists the lowest %u)",
+                        (unsigned long long)check_res.n_bad, info.n_bits, (unsigned long long)N,
+                        (unsigned long long)check_res.rows[0], (unsigned)ZKGPU_CHECK_MAX_ROWS);
+        return 0;
+    }
+    int check_readback()
+    {
+        uint64_t h[4 + ZKGPU_CHECK_MAX_ROWS];
+        CK(zkgpu_memcpy_d2h(h, check_dev, sizeof h));
+        check_res.n_bad = h[0];
+        memcpy(check_res.rows, h + 1, ZKGPU_CHECK_MAX_ROWS * 8);
+        for (int k = 0; k < 3; k++) check_res.value[k] = h[1 + ZKGPU_CHECK_MAX_ROWS + k] % P;
+        check_res.ran = 1;
+        check_pending = false;
+        return 0;
+    }
+    int check_result(zkgpu_check_result *out) const
+    {
+        if (!out) return fail("check_result: null buffer");
+        *out = check_res;
+        return 0;
+    }
+
     // ---- the steps of prove_body that the row-sharded prover overrides
     // (with quotient_pieces, h1h2_all, z_all, ncol, r0 and the FRI steps)
 
@@ -1231,6 +1339,8 @@ public:
     int prove_body(uint64_t *out)
     {
         probe_valid = false;
+        check_pending = false;
+        check_res = zkgpu_check_result{};
         timers.clear();
         pend_t.clear();
         pend_x.clear();
@@ -1289,6 +1399,7 @@ public:
             if (run_prog(ZKGPU_PROBE_STEP3, step3, ch, evals)) return -1;
             if (tstop("STARK_STEP_3_CALCULATE_EXPS_2")) return -1;
         }
+        if (check_mode != ZKGPU_CHECK_OFF && check_run(tr, ch)) return -1;
         if (commit_root(3)) return -1;
         // STAGE 4 (:226-296)
         tr.get_field(ch + 12);
@@ -1345,6 +1456,7 @@ public:
         if (run_prog(ZKGPU_PROBE_STEP52NS, step52ns, ch, evals) || fill_fri_pol0()) return -1;
         if (tstop("STARK_STEP_5_CALCULATE_EXPS")) return -1;
         if (fri_and_queries(tr, &roots[0][0], evals, out, tall)) return -1;
+        if (check_pending && check_readback()) return -1;
         return probe_readback();
     }
 
@@ -1677,6 +1789,8 @@ int zkgpu_stark_probe_set(void *h, const uint64_t *rows_n, uint32_t n_rows_n, co
 {
     return ((Starks *)h)->probe_set(rows_n, n_rows_n, rows_ext, n_rows_ext);
 }
+int zkgpu_stark_check_set(void *h, uint32_t mode) { return ((Starks *)h)->check_set(mode); }
+int zkgpu_stark_check_result(void *h, zkgpu_check_result *out) { return ((Starks *)h)->check_result(out); }
 int zkgpu_stark_probe_size(void *h, uint32_t *n_recs, uint64_t *n_words)
 {
     return ((Starks *)h)->probe_size(n_recs, n_words);

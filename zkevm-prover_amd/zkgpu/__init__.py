@@ -91,6 +91,8 @@ _SIGS = {
     "zkgpu_rand_cols_rows_dev": (ctypes.c_int, [vp, u64, vp, u32, u64, u64, u32, u64, u64]),
     "zkgpu_copy_rows_dev": (ctypes.c_int, [vp, u64, u64, vp, vp, u64, u64, u32, vp, u32, u64]),
     "zkgpu_gather_rows_dev": (ctypes.c_int, [vp, vp, u64, u32, vp, u64]),
+    "zkgpu_nonzero_rows_dev": (ctypes.c_int, [vp, vp, u64, u32, u64, u32]),
+    "zkgpu_zxp_to_n_domain": (ctypes.c_int, [vp, vp, u32, vp, u32, u32]),
     "zkgpu_device_memory": (ctypes.c_int, [pu64, pu64]),
     "zkgpu_lde_workspace_bytes": (u64, [u64, u64, u64]),
     "zkgpu_zxp_eval_dev": (ctypes.c_int, [vp, u32, vp, u32, u32, u32, vp, u32, vp, vp, u32, vp, u32, vp, vp, u32,
@@ -407,6 +409,26 @@ def gather_rows_dev(out, src, ld, ncols, rows, nrows):
     row-major block"""
     _check(lib().zkgpu_gather_rows_dev(_addr(out), _addr(src), ld, ncols, _addr(rows), nrows),
            "zkgpu_gather_rows_dev")
+
+
+def nonzero_rows_dev(out, cols, ld, ncols, n, max_rows):
+    """out (device, 1 + max_rows words): out[0] = the number of rows i < n of
+    the column-major section `cols` with a word != 0 (mod p) in some column,
+    out[1:] = the lowest max_rows of them, ascending, 2^64 - 1 past the last
+    (zkgpu_nonzero_rows_dev; queued on the library stream)"""
+    _check(lib().zkgpu_nonzero_rows_dev(_addr(out), _addr(cols), ld, ncols, n, max_rows), "zkgpu_nonzero_rows_dev")
+
+
+def zxp_to_n_domain(ins, opn, extend_bits):
+    """The operand table of a quotient program (step42ns: ins, opn as
+    prog.arrays() gives them) re-targeted to the trace domain
+    (zkgpu_zxp_to_n_domain, no GPU needed); the instruction list is unchanged"""
+    ins = np.ascontiguousarray(ins, np.uint32).reshape(-1, 4)
+    opn = np.ascontiguousarray(opn, np.uint32).reshape(-1, 4)
+    out = np.zeros((max(opn.shape[0], 1), 4), np.uint32)
+    _check(lib().zkgpu_zxp_to_n_domain(out.ctypes.data, ins.ctypes.data, ins.shape[0], opn.ctypes.data, opn.shape[0],
+                                       extend_bits), "zkgpu_zxp_to_n_domain")
+    return out[:opn.shape[0]]
 
 
 def rows_to_cols_dev(cols, ld, rows, nrows, ncols):

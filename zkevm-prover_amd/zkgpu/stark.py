@@ -54,6 +54,17 @@ class Comm(ctypes.Structure):
                 ("exchange", EXCHANGE), ("abort", ABORT)]
 
 
+# constraint check (include/zkgpu_stark.h ZKGPU_CHECK_*)
+CHECK_OFF, CHECK_REPORT, CHECK_STOP = 0, 1, 2
+CHECK_MAX_ROWS = 16
+
+
+class CheckResult(ctypes.Structure):
+    """zkgpu_check_result (include/zkgpu_stark.h)"""
+    _fields_ = [("ran", ctypes.c_uint32), ("n_bad", ctypes.c_uint64), ("rows", ctypes.c_uint64 * CHECK_MAX_ROWS),
+                ("value", ctypes.c_uint64 * 3), ("alpha", ctypes.c_uint64 * 3)]
+
+
 _slib = None
 
 
@@ -84,6 +95,8 @@ def slib():
             ("zkgpu_stark_probe_set", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp, ctypes.c_uint32]),
             ("zkgpu_stark_probe_size", ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(u64)]),
             ("zkgpu_stark_probe_read", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp, u64]),
+            ("zkgpu_stark_check_set", ctypes.c_int, [vp, ctypes.c_uint32]),
+            ("zkgpu_stark_check_result", ctypes.c_int, [vp, ctypes.POINTER(CheckResult)]),
             ("zkgpu_stark_create_sharded", ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(_Info),
                                                           ctypes.POINTER(Comm)]),
             ("zkgpu_stark_memory_plan", ctypes.c_int, [ctypes.POINTER(_Info), ctypes.c_uint32,
@@ -432,6 +445,22 @@ class GpuStark:
             vals = payload[r.vals_off:r.vals_off + r.n_rows * r.ncols].reshape(r.n_rows, r.ncols).copy()
             out.append((r.point, r.after, r.section, rows, vals))
         return out
+
+    def check_set(self, mode):
+        """constraint check of every later proof (zkgpu_stark_check_set):
+        CHECK_OFF, CHECK_REPORT (the result after the proof, check_result) or
+        CHECK_STOP (prove fails at the check when a row breaks the AIR)"""
+        _check(slib().zkgpu_stark_check_set(self.h, mode), "zkgpu_stark_check_set")
+
+    def check_result(self):
+        """the last proof's constraint check: dict(ran, n_bad, rows (the lowest
+        CHECK_MAX_ROWS failing rows, ascending), value (C at rows[0]), alpha
+        (the combination challenge the check used))"""
+        r = CheckResult()
+        _check(slib().zkgpu_stark_check_result(self.h, ctypes.byref(r)), "zkgpu_stark_check_result")
+        rows = [int(x) for x in r.rows if x != 2**64 - 1]
+        return {"ran": int(r.ran), "n_bad": int(r.n_bad), "rows": rows, "value": [int(x) for x in r.value],
+                "alpha": [int(x) for x in r.alpha]}
 
     def timers(self):
         names = ctypes.create_string_buffer(4096)
