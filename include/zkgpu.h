@@ -210,7 +210,8 @@ int zkgpu_load_wait(void *ticket);
 /* MerkleTreeGL::getGroupProof(Element *proof, uint64_t idx) for nq queries at
  * once -- merkleTreeGL.cpp:12-35, friProve.cpp:195-232.
  * vals_out: nq x ncols, sibs_out: nq x log2(nrows) x 4 (host pointers);
- * src column-major on device (ld), nodes on device. */
+ * src column-major on device (ld), nodes on device.  ZKGPU_ERR_ARG, with
+ * nothing queued, when nrows is not a power of two or an index is >= nrows. */
 int zkgpu_gl_merkle_open_dev(uint64_t *vals_out, uint64_t *sibs_out, const uint64_t *nodes, const uint64_t *src,
                              uint64_t ld, uint64_t ncols, uint64_t nrows, const uint64_t *idx, uint64_t nq);
 
@@ -421,7 +422,12 @@ int zkgpu_calculate_z_many_dev(const zkgpu_z_req *req, uint32_t nz, uint64_t n, 
 /* Starks::evmap (starks.cpp:556-669): evals[e] = sum_{k<n} L(k) * pol_e[k << extend_bits],
  * L = lev or lpev (device, 3 columns of ld l_ld).  cols = host array of device
  * column pointers (first column of each polynomial), lds / dims / primes per
- * entry.  evals_out: host (n_ev x 3). */
+ * entry.  evals_out: host (n_ev x 3).  A row block of longer columns is the
+ * same call with the pointers advanced (lev + k0, col + (k0 << extend_bits))
+ * and the leading dimensions kept.  ZKGPU_ERR_ARG, with nothing queued, when
+ * l_ld < n or when the lds[e] of a dim-3 entry cannot hold the
+ * ((n - 1) << extend_bits) + 1 rows read (a dim-1 entry's is not used);
+ * n = 0 writes zero evaluations and launches nothing. */
 int zkgpu_evmap_dev(uint64_t *evals_out, const uint64_t *const *cols, const uint64_t *lds, const uint32_t *dims,
                     const uint32_t *primes, uint32_t n_ev, const uint64_t *lev, const uint64_t *lpev, uint64_t l_ld,
                     uint64_t n, uint32_t extend_bits);
@@ -476,7 +482,8 @@ int zkgpu_h1h2_dev(uint64_t *h1, uint64_t h1_ld, uint64_t *h2, uint64_t h2_ld, c
 /* 3 ext columns (ld >= n) -> interleaved n x 3 (the FRI polynomial layout, friProve.cpp) */
 int zkgpu_cols3_to_interleaved_dev(uint64_t *out, const uint64_t *cols, uint64_t ld, uint64_t n);
 
-/* MerkleTreeGL::getGroupProof for a row-major device source (FRI trees) */
+/* MerkleTreeGL::getGroupProof for a row-major device source (FRI trees); the
+ * same refusals as zkgpu_gl_merkle_open_dev */
 int zkgpu_gl_merkle_open_rows_dev(uint64_t *vals_out, uint64_t *sibs_out, const uint64_t *nodes, const uint64_t *src,
                                   uint64_t ncols, uint64_t nrows, const uint64_t *idx, uint64_t nq);
 

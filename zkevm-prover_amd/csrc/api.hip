@@ -603,6 +603,8 @@ int zkgpu_gl_merkle_open_dev(uint64_t *vals_out, uint64_t *sibs_out, const uint6
     if ((rc = require_init())) return rc;
     if (!nq) return 0;
     Ctx &c = g_ctx;
+    if (nrows == 0 || (nrows & (nrows - 1)))
+        return set_error(ZKGPU_ERR_ARG, "merkle_open: nrows %llu is not a power of two", (unsigned long long)nrows);
     uint32_t nlev = log2u(nrows);
     for (uint64_t q = 0; q < nq; q++)
         if (idx[q] >= nrows) return set_error(ZKGPU_ERR_ARG, "merkle_open: index %llu >= nrows", (unsigned long long)idx[q]);
@@ -1243,6 +1245,21 @@ int zkgpu_evmap_dev(uint64_t *evals_out, const uint64_t *const *cols, const uint
     int rc;
     if ((rc = require_init())) return rc;
     if (!n_ev) return 0;
+    for (uint32_t e = 0; e < n_ev; e++)
+        if (dims[e] != 1 && dims[e] != 3) return set_error(ZKGPU_ERR_ARG, "evmap: entry %u dim %u", e, dims[e]);
+    if (!n) {  // an empty row block: every sum is zero, nothing to launch
+        memset(evals_out, 0, (size_t)n_ev * 24);
+        return 0;
+    }
+    if (l_ld < n) return set_error(ZKGPU_ERR_ARG, "evmap: l_ld < n");
+    if (extend_bits > 63 || ((n - 1) << extend_bits) >> extend_bits != n - 1)
+        return set_error(ZKGPU_ERR_ARG, "evmap: rows << extend_bits beyond 2^64");
+    // a dim-3 entry's components lie lds[e] apart: each must hold the last row read
+    const uint64_t span = ((n - 1) << extend_bits) + 1;
+    for (uint32_t e = 0; e < n_ev; e++)
+        if (dims[e] == 3 && lds[e] < span)
+            return set_error(ZKGPU_ERR_ARG, "evmap: entry %u: ld %llu < %llu rows", e, (unsigned long long)lds[e],
+                             (unsigned long long)span);
     // sub-entries: a dim-1 entry is one, a dim-3 entry three (component j,
     // weighted by X^j when the sums are combined); grouped by L (prime or not)
     // into EV_G-wide groups
@@ -1258,10 +1275,8 @@ int zkgpu_evmap_dev(uint64_t *evals_out, const uint64_t *const *cols, const uint
         uint32_t prime, which, entry;
     };
     std::vector<Sub> subs;
-    for (uint32_t e = 0; e < n_ev; e++) {
-        if (dims[e] != 1 && dims[e] != 3) return set_error(ZKGPU_ERR_ARG, "evmap: entry %u dim %u", e, dims[e]);
+    for (uint32_t e = 0; e < n_ev; e++)
         for (uint32_t j = 0; j < dims[e]; j++) subs.push_back(Sub{cols[e] + (uint64_t)j * lds[e], primes[e] ? 1u : 0u, j, e});
-    }
     std::stable_sort(subs.begin(), subs.end(), [](const Sub &a, const Sub &b) { return a.prime < b.prime; });
     std::vector<G> groups;
     std::vector<int32_t> sub_of(3 * (size_t)n_ev, -1);
@@ -1486,9 +1501,12 @@ int zkgpu_gl_merkle_open_rows_dev(uint64_t *vals_out, uint64_t *sibs_out, const 
     if ((rc = require_init())) return rc;
     if (!nq) return 0;
     Ctx &c = g_ctx;
+    if (nrows == 0 || (nrows & (nrows - 1)))
+        return set_error(ZKGPU_ERR_ARG, "merkle_open_rows: nrows %llu is not a power of two", (unsigned long long)nrows);
     uint32_t nlev = log2u(nrows);
     for (uint64_t q = 0; q < nq; q++)
-        if (idx[q] >= nrows) return set_error(ZKGPU_ERR_ARG, "merkle_open: index out of range");
+        if (idx[q] >= nrows)
+            return set_error(ZKGPU_ERR_ARG, "merkle_open_rows: index %llu >= nrows", (unsigned long long)idx[q]);
     size_t nv = nq * ncols, ns = nq * nlev * 4;
     uint64_t *d = workspace(2, (nq + nv + ns + 1) * sizeof(uint64_t));
     if (!d) return ZKGPU_ERR_OOM;
