@@ -378,6 +378,47 @@ int zkgpu_zxp_compile(const void *instr, uint32_t n_instr, const void *opnd, uin
 int zkgpu_zxp_to_n_domain(zxp_operand *opnd_out, const zxp_instr *instr, uint32_t n_instr,
                           const zxp_operand *opnd, uint32_t n_opnd, uint32_t extend_bits);
 
+/* The constraint combination of a quotient program taken apart into its terms (csrc/zxp_split.cpp,
+ * which states the rule).  instr/opnd: step42ns as given or as rewritten by zkgpu_zxp_to_n_domain;
+ * chal: the index of the combination challenge (4).  Outputs: a TAPPED program -- the source's
+ * instructions that touch no combination, verbatim and in order, and where term k joins the
+ * combination "COPY COL3(SEC_Q_2NS, 3k) <- x"; the final store to q is dropped -- over an operand
+ * table that is the source's followed by the taps' operands, and the term table.  Per row the tapped
+ * program's 3 * n_terms output columns hold the values v_k with
+ *     C = sum over the terms k that are not dead of (-1)^negated_k * alpha^exponent_k * v_k
+ * exactly, C being the value the source stores to q (without its factor ZI).  The k-th term is the
+ * k-th identity folded, in the producer's order; terms[k].instr is the source instruction where it
+ * joined.  Buffer sizes (at most two taps per source instruction): instr_out 2 * n_instr, opnd_out
+ * n_opnd + 2 * n_instr + 1, terms 2 * n_instr; the counts written are what was used.  The temp
+ * counts are the source's.  ZKGPU_ERR_ARG with a message naming the instruction: a combination
+ * multiplied by anything but the challenge (ZI or the literal 1 at the store to q excepted; a product
+ * into a TMP3 slot whose value reaches no combination and no column is dropped instead), written to
+ * a TMP1 slot, to a column other than COL3(SEC_Q_2NS, 0, shift 0) or there by an ADD / SUB / product
+ * by the challenge, two combinations that share a term added, a store to SEC_Q_2NS that is free of
+ * the challenge, a second store to q or none, indices out of range.  No GPU needed. */
+int zkgpu_zxp_split_constraints(zxp_instr *instr_out, uint32_t *n_instr_out, zxp_operand *opnd_out,
+                                uint32_t *n_opnd_out, zxp_split_term *terms, uint32_t *n_terms,
+                                const zxp_instr *instr, uint32_t n_instr, const zxp_operand *opnd,
+                                uint32_t n_opnd, uint32_t chal);
+
+/* zkgpu_zxp_eval_dev at a LIST OF ROWS held in device memory: for every j < n_rows with
+ * rows[j] < 2^log_dom the program is evaluated at row i = rows[j] -- column reads at
+ * (i + shift) mod 2^log_dom of the section, X / ZI / XDIV / XDIVW at i -- and its column STORES go to
+ * index j of the destination column, so a section the program stores to is compact: ld >= n_rows.
+ * An entry rows[j] >= 2^log_dom writes nothing at index j (zkgpu_nonzero_rows_dev pads its list
+ * with UINT64_MAX); the list may be unsorted and hold repeats.  The other arguments are those of
+ * zkgpu_zxp_eval_dev.  Always the interpreter (k_zxp_eval_rows, csrc/stark.hip), after the same
+ * argument checks, compile and LDS bound; enqueued on the library stream with NO host
+ * synchronisation (the records go up from pinned staging buffers that are reused once their copy
+ * has completed).  ZKGPU_ERR_ARG, nothing queued: a section that is both read and stored to, a
+ * store at a row shift, a store section with ld < n_rows, n_rows > 4096, null rows.  n_rows = 0
+ * queues nothing. */
+int zkgpu_zxp_eval_rows_dev(const void *instr, uint32_t n_instr, const void *opnd, uint32_t n_opnd, uint32_t n_tmp1,
+                            uint32_t n_tmp3, const zkgpu_sections *sections, uint32_t log_dom,
+                            const uint64_t *challenges, const uint64_t *publics, uint32_t n_publics,
+                            const uint64_t *evals, uint32_t n_evals, const uint64_t *xdiv, const uint64_t *xdivw,
+                            uint32_t extend_bits, uint64_t x_start, const uint64_t *rows, uint32_t n_rows);
+
 /* Diagnostics for the run-time compiled expression kernels (csrc/zxp_jit.hip):
  * compile a program exactly as zkgpu_zxp_eval_dev does and write the
  * generated straight-line HIP kernel source into buf (truncated to buflen);

@@ -206,7 +206,8 @@ int zkgpu_stark_probe_read(void *handle, zkgpu_probe_rec *recs, uint32_t max_rec
  * memory plan), and reduce it to the rows where C != 0
  * (zkgpu_nonzero_rows_dev).  C vanishes on every row iff every identity holds
  * there, with overwhelming probability over the combination challenge.  The
- * check names ROWS, not constraints.
+ * check itself names ROWS; zkgpu_stark_check_names_set (below) adds the
+ * constraints that fail at them.
  *
  * The combination challenge: the transcript's challenge 4 is drawn from root 3,
  * which does not exist yet, so the check uses the getField of a COPY of the
@@ -236,6 +237,31 @@ typedef struct {
 } zkgpu_check_result;
 int zkgpu_stark_check_set(void *handle, uint32_t mode);
 int zkgpu_stark_check_result(void *handle, zkgpu_check_result *out);
+
+/* Naming: which identities fail at the listed rows.  step42ns folds its identities into C with
+ * powers of the combination challenge; zkgpu_zxp_split_constraints (include/zkgpu.h) takes that
+ * combination apart into terms -- the k-th term is the k-th identity folded, in the producer's
+ * (pil-stark's) order, and terms[k].instr is the step42ns instruction at which it joined -- and
+ * with naming on a checked proof also evaluates every term at the check's listed rows: ONE more
+ * launch (zkgpu_zxp_eval_rows_dev, kernel k_zxp_eval_rows, whose waves return at once when no row
+ * is listed) behind the check's, into a device block of 3 x n_terms x 16 words allocated by
+ * names_set outside the memory plan.  REPORT still adds no synchronisation inside the proof; the
+ * block is read back with the check's result, and only when n_bad > 0.  The row result
+ * (zkgpu_check_result) is unchanged, and with naming off a checked proof queues what it queued
+ * before.  STOP's failure message gains a tail naming up to 8 failing terms at the first row.
+ *   names_set    on != 0: splits the n-domain step42ns once; a program the split refuses makes it fail
+ *                with that message and leaves naming off (the row check is unaffected).  Refused:
+ *                a sharded prover.  Holds for every later checked proof until changed.
+ *   check_terms  the term table: *n = n_terms, min(max, n_terms) entries written.
+ *   check_named  for the failing row rows[slot] (slot < 16) of the last checked proof: *n_failing =
+ *                the number of live terms that are not zero there, and the first min(max, that)
+ *                of them: ids ascending, values canonical (3 words each).  C at that row is the
+ *                sum of (-1)^negated * alpha^exponent * value over them.  A slot past the last
+ *                failing row is empty.  Fails when the last proof ran no check with naming on. */
+int zkgpu_stark_check_names_set(void *handle, int on);
+int zkgpu_stark_check_terms(void *handle, zxp_split_term *out, uint32_t max, uint32_t *n);
+int zkgpu_stark_check_named(void *handle, uint32_t slot, uint32_t *ids, uint64_t *values, uint32_t max,
+                            uint32_t *n_failing);
 
 /* ---- the Fiat-Shamir transcript the prover runs on the host, as the
  * reference's class Transcript (transcript.hpp:14-37, transcript.cpp:4-88):

@@ -122,4 +122,15 @@ typedef struct {
     uint32_t domain_ext;     /* 0: n-domain, 1: 2n-domain */
 } zxp_program;
 
+/* One term of a quotient program's constraint combination
+ * (zkgpu_zxp_split_constraints, include/zkgpu.h): term k enters the value
+ * stored to q as (-1)^negated * alpha^exponent * v_k, v_k being what the
+ * tapped program stores to COL3(SEC_Q_2NS, 3k). */
+typedef struct {
+    uint32_t exponent; /* power of the combination challenge in the stored value */
+    uint32_t negated;  /* 1: it enters with a minus sign */
+    uint32_t instr;    /* source instruction at which the term joined */
+    uint32_t dead;     /* 1: it never reaches q (exponent = negated = 0) */
+} zxp_split_term;
+
 #endif /* ZKGPU_ZXP_H */

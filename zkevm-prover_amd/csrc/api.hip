@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <new>
@@ -1162,6 +1163,112 @@ int zkgpu_zxp_eval_dev(const void *instr, uint32_t n_instr, const void *opnd, ui
     return zxp_eval_run(ZxpArgs{(const zxp_instr *)instr, n_instr, (const zxp_operand *)opnd, n_opnd, n_tmp1, n_tmp3,
                                 sections, log_dom, log_dom, 1, challenges, publics, n_publics, evals, n_evals, xdiv,
                                 xdivw, extend_bits, x_start});
+}
+
+// zkgpu_zxp_eval_rows_dev runs inside a proof that must not wait for the host,
+// so its records go up from PINNED staging buffers: a pair (host, device) of
+// the current device is taken -- marked busy under the lock -- when it is
+// large enough, not in a caller's hands, and the event recorded behind its
+// last launch has completed; another pair is made when there is none (a
+// hipMalloc waits for nothing).  The pairs sit in a deque, so a pair's address
+// holds while others are added.  They live as long as the process, like
+// g_param and the zhInv tables: at most one per call in flight, each of the
+// size of one program's records.
+struct RowsStage {
+    int device;
+    char *host, *dev;
+    size_t bytes;
+    hipEvent_t done;
+    bool busy;  // between rows_stage and rows_stage_done
+};
+static std::deque<RowsStage> g_rows_stages;
+static std::mutex g_rows_stages_mu;
+static RowsStage *rows_stage(size_t bytes)
+{
+    std::lock_guard<std::mutex> lk(g_rows_stages_mu);
+    for (RowsStage &r : g_rows_stages)
+        if (r.device == g_ctx.device && !r.busy && r.bytes >= bytes && hipEventQuery(r.done) == hipSuccess) {
+            r.busy = true;
+            return &r;
+        }
+    RowsStage r{g_ctx.device, nullptr, nullptr, std::max<size_t>(bytes, 1 << 16), nullptr, true};
+    if (hipHostMalloc((void **)&r.host, r.bytes, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc((void **)&r.dev, r.bytes) != hipSuccess ||
+        hipEventCreateWithFlags(&r.done, hipEventDisableTiming) != hipSuccess) {
+        if (r.host) (void)hipHostFree(r.host);
+        if (r.dev) (void)hipFree(r.dev);
+        return nullptr;
+    }
+    g_rows_stages.push_back(r);
+    return &g_rows_stages.back();
+}
+// the caller is through with the pair: what it queued on s (if anything) ends at the event
+static int rows_stage_done(RowsStage *st, hipStream_t s, bool queued)
+{
+    const int rc = queued ? check_hip(hipEventRecord(st->done, s), "zxp rows: event") : 0;
+    std::lock_guard<std::mutex> lk(g_rows_stages_mu);
+    st->busy = false;
+    return rc;
+}
+
+// One evaluation at a list of rows: the phases of zxp_eval_run, always the
+// interpreter, no host synchronisation.
+static int zxp_eval_rows_run(const ZxpArgs &a)
+{
+    int rc;
+    if ((rc = require_init()) || (rc = zxp_validate(a))) return rc;
+    if (!a.n_rows) return 0;
+    ZxpPlan P;
+    if ((rc = zxp_plan(a, P))) return rc;
+    hipStream_t s = g_ctx.stream;
+    const size_t off_terms = (size_t)std::max<uint32_t>(P.prog.n_instr, 1) * sizeof(ZOp);
+    const size_t off_zh = off_terms + (size_t)P.n_dot_terms * sizeof(ZTerm);
+    const size_t bytes = off_zh + P.n_zhinv * 8;
+    RowsStage *st = rows_stage(bytes);
+    if (!st) return set_error(ZKGPU_ERR_OOM, "zxp rows: staging buffers");
+    std::vector<ZOp> ops;
+    std::vector<ZTerm> terms;
+    if ((rc = zxp_records(a, P, (const uint64_t *)(st->dev + off_zh), ops, terms))) {
+        (void)rows_stage_done(st, s, false);
+        return rc;
+    }
+    if (ops.size()) memcpy(st->host, ops.data(), ops.size() * sizeof(ZOp));
+    if (terms.size()) memcpy(st->host + off_terms, terms.data(), terms.size() * sizeof(ZTerm));
+    memcpy(st->host + off_zh, P.zhinv, P.n_zhinv * 8);
+    if ((rc = check_hip(hipMemcpyAsync(st->dev, st->host, bytes, hipMemcpyHostToDevice, s), "H2D"))) {
+        (void)rows_stage_done(st, s, true);
+        return rc;
+    }
+    ZxpLaunch L;
+    L.prog = (const ZOp *)st->dev;
+    L.terms = (const ZTerm *)(st->dev + off_terms);
+    L.n_instr = P.prog.n_instr;
+    L.n_tmp1 = P.prog.n_tmp1;
+    L.n_tmp3 = P.prog.n_tmp3;
+    L.logdom = a.log_dom;
+    L.logomega = a.log_omega;
+    L.wrap = 1;
+    L.x_start = a.x_start % HP;
+    L.bytes = P.bytes;
+    rc = zxp_eval_rows(L, a.rows, a.n_rows, s);
+    // (recorded after a failed launch too: the copy still reads the host buffer)
+    const int rc2 = rows_stage_done(st, s, true);
+    return rc ? rc : rc2;
+}
+
+int zkgpu_zxp_eval_rows_dev(const void *instr, uint32_t n_instr, const void *opnd, uint32_t n_opnd, uint32_t n_tmp1,
+                            uint32_t n_tmp3, const zkgpu_sections *sections, uint32_t log_dom,
+                            const uint64_t *challenges, const uint64_t *publics, uint32_t n_publics,
+                            const uint64_t *evals, uint32_t n_evals, const uint64_t *xdiv, const uint64_t *xdivw,
+                            uint32_t extend_bits, uint64_t x_start, const uint64_t *rows, uint32_t n_rows)
+{
+    ZxpArgs a{(const zxp_instr *)instr, n_instr, (const zxp_operand *)opnd, n_opnd, n_tmp1, n_tmp3,
+              sections, log_dom, log_dom, 1, challenges, publics, n_publics, evals, n_evals, xdiv,
+              xdivw, extend_bits, x_start};
+    a.row_list = true;
+    a.rows = rows;
+    a.n_rows = n_rows;
+    return zxp_eval_rows_run(a);
 }
 
 int zkgpu_zxp_eval_block_dev(const void *instr, uint32_t n_instr, const void *opnd, uint32_t n_opnd, uint32_t n_tmp1,

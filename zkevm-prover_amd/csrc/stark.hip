@@ -293,14 +293,14 @@ __device__ __forceinline__ Val zxp_load(const ZxpEnv &e, uint32_t kind, const ui
 
 // One wave per workgroup, one row per lane.  Instruction k is one pre-decoded
 // 128-byte ZOp record read with scalar loads; operands, op and destination
-// are all wave-uniform branches.
-__global__ void __launch_bounds__(ZXP_THREADS) k_zxp_eval(ZxpEnv e)
+// are all wave-uniform branches.  The lane evaluates row i (reads, X, ZI,
+// XDIV at i; nothing is stored unless it is active); ROWS: the row came from a
+// list and a column store goes to index j of the destination, the lane's
+// place in the list.
+template <bool ROWS>
+__device__ __forceinline__ void zxp_eval_body(const ZxpEnv &e, uint64_t *zlds, const int lane, const uint64_t i,
+                                              const bool active, const uint64_t j)
 {
-    extern __shared__ __attribute__((aligned(16))) uint64_t zlds[];
-    const int lane = threadIdx.x;
-    const uint64_t i = (uint64_t)blockIdx.x * ZXP_THREADS + lane;
-    const uint64_t dom = 1ULL << e.logdom;
-    const bool active = i < dom;
     const uint64_t ir = active ? i : 0;
     const uint64_t dmask = e.rmask;
     for (uint32_t k = 0; k < e.n_instr; k++) {
@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(ZXP_THREADS) k_zxp_eval(ZxpEnv e)
         case DK_C1:
         case DK_C3:
             if (active) {
-                uint64_t *p = z.pd + ((i + (uint64_t)(int64_t)z.id) & e.rmask);
+                uint64_t *p = ROWS ? z.pd + j : z.pd + ((i + (uint64_t)(int64_t)z.id) & e.rmask);
                 p[0] = gl_canon(r.v.v[0]);
                 if (z.kd == DK_C3) {
                     p[z.ldd] = r.dim == 3 ? gl_canon(r.v.v[1]) : 0;
@@ -388,6 +388,31 @@ __global__ void __launch_bounds__(ZXP_THREADS) k_zxp_eval(ZxpEnv e)
         default: break;
         }
     }
+}
+
+__global__ void __launch_bounds__(ZXP_THREADS) k_zxp_eval(ZxpEnv e)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t zlds[];
+    const int lane = threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * ZXP_THREADS + lane;
+    zxp_eval_body<false>(e, zlds, lane, i, i < (1ULL << e.logdom), 0);
+}
+
+// The same at a list of rows (zkgpu_zxp_eval_rows_dev): lane j of the grid
+// takes row rows[j]; an entry past the domain (zkgpu_nonzero_rows_dev pads
+// its list with UINT64_MAX) and a lane past the list are not active.  Stores
+// go to pd + j: consecutive lanes, consecutive words.  A wave with no active
+// lane -- every wave of the constraint check's launch over a clean trace --
+// returns before its first instruction.
+__global__ void __launch_bounds__(ZXP_THREADS) k_zxp_eval_rows(ZxpEnv e, const uint64_t *rows, uint32_t n_rows)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t zlds[];
+    const int lane = threadIdx.x;
+    const uint64_t j = (uint64_t)blockIdx.x * ZXP_THREADS + lane;
+    const uint64_t i = j < n_rows ? rows[j] : ~0ULL;
+    const bool active = i < (1ULL << e.logdom);
+    if (!__ballot(active)) return;  // (one wave per workgroup, no barrier in the body)
+    zxp_eval_body<true>(e, zlds, lane, i, active, j);
 }
 
 // ---------------------------------------------------------------- calculateZ
@@ -824,7 +849,8 @@ static int nonzero_rows(uint64_t *out, uint32_t *counts, const uint64_t *cols, u
     return check_launch("k_nz_emit");
 }
 
-int zxp_eval(const ZxpLaunch &L, hipStream_t s)
+// the interpreter's environment and LDS bytes of one launch (both kernels)
+static ZxpEnv zxp_env(const ZxpLaunch &L, bool wrap, size_t &lds)
 {
     Ctx &c = ctx();
     ZxpEnv e;
@@ -833,17 +859,35 @@ int zxp_eval(const ZxpLaunch &L, hipStream_t s)
     e.n_instr = L.n_instr;
     e.logdom = L.logdom;
     e.logomega = L.logomega;
-    e.rmask = L.wrap ? (1ULL << L.logdom) - 1 : ~0ULL;
+    e.rmask = wrap ? (1ULL << L.logdom) - 1 : ~0ULL;
     e.x_start = L.x_start;
     e.tw_lo = c.tw_lo[0];
     e.tw_hi = c.tw_hi[0];
     const uint64_t slots = (uint64_t)L.n_tmp1 + 3ULL * L.n_tmp3;  // within LDS: zxp_records (csrc/zxp_prepare.cpp)
-    const size_t lds = (size_t)(slots ? slots : 1) * ZXP_THREADS * sizeof(uint64_t);
+    lds = (size_t)(slots ? slots : 1) * ZXP_THREADS * sizeof(uint64_t);
+    return e;
+}
+
+int zxp_eval(const ZxpLaunch &L, hipStream_t s)
+{
+    size_t lds;
+    const ZxpEnv e = zxp_env(L, L.wrap, lds);
     const uint64_t dom = 1ULL << L.logdom;
     prof_begin(s);
     hipLaunchKernelGGL(k_zxp_eval, dim3(nblk(dom, ZXP_THREADS)), dim3(ZXP_THREADS), lds, s, e);
     prof_end("k_zxp_eval", L.bytes, s);
     return check_launch("k_zxp_eval");
+}
+
+int zxp_eval_rows(const ZxpLaunch &L, const uint64_t *rows, uint32_t n_rows, hipStream_t s)
+{
+    if (!n_rows) return 0;
+    size_t lds;
+    const ZxpEnv e = zxp_env(L, true, lds);  // a row list is of the whole domain: shifted reads wrap
+    prof_begin(s);
+    hipLaunchKernelGGL(k_zxp_eval_rows, dim3(nblk(n_rows, ZXP_THREADS)), dim3(ZXP_THREADS), lds, s, e, rows, n_rows);
+    prof_end("k_zxp_eval_rows", L.bytes, s);
+    return check_launch("k_zxp_eval_rows");
 }
 
 size_t calculate_z_scratch_words(uint64_t n)

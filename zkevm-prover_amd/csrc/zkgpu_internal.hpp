@@ -110,6 +110,8 @@ int rand_cols(uint64_t *base, uint64_t ld, const uint32_t *cols_dev, uint32_t nc
 int copy_rows(uint64_t *dst, uint64_t dld, uint64_t drow0, const uint32_t *dcols, const uint64_t *src, uint64_t sld,
               uint64_t srow0, uint64_t smask, const uint32_t *scols, uint32_t ncols, uint64_t nrows, hipStream_t s);
 int zxp_eval(const ZxpLaunch &L, hipStream_t s);
+// the same at the rows rows[0 .. n_rows) (device), stores compact (k_zxp_eval_rows)
+int zxp_eval_rows(const ZxpLaunch &L, const uint64_t *rows, uint32_t n_rows, hipStream_t s);
 size_t calculate_z_scratch_words(uint64_t n);
 int calculate_z(uint64_t *z, uint64_t z_ld, const uint64_t *num, uint64_t num_ld, const uint64_t *den,
                 uint64_t den_ld, uint64_t n, const uint64_t z0[3], uint64_t *scratch, uint64_t *total_dev, hipStream_t s);

@@ -23,6 +23,37 @@ int zxp_validate(const ZxpArgs &a)
             return set_error(ZKGPU_ERR_ARG, "zxp: instruction %u out of range", k);
     }
     const zkgpu_sections &S = *a.sections;
+    // a row list: the rows read are rows of the whole section, the rows stored are the list's
+    // places, so a section is one or the other, and what is stored to is n_rows long
+    bool stored[SEC_COUNT] = {};
+    if (a.row_list) {
+        if (!a.rows) return set_error(ZKGPU_ERR_ARG, "zxp rows: null row list");
+        if (a.n_rows > ZXP_MAX_LIST_ROWS)
+            return set_error(ZKGPU_ERR_ARG, "zxp rows: %u rows exceed %u", a.n_rows, ZXP_MAX_LIST_ROWS);
+        bool read[SEC_COUNT] = {};
+        const auto col = [&](uint32_t k) {
+            const zxp_operand &o = a.opnd[k];
+            return (o.kind == ZXP_COL || o.kind == ZXP_COL3) && o.a < SEC_COUNT;
+        };
+        for (uint32_t k = 0; k < a.n_instr; k++) {
+            const zxp_instr &I = a.instr[k];
+            if (col(I.a)) read[a.opnd[I.a].a] = true;
+            if (I.op != ZXP_COPY && col(I.b)) read[a.opnd[I.b].a] = true;
+            if (col(I.dst)) {
+                if (a.opnd[I.dst].c)
+                    return set_error(ZKGPU_ERR_ARG, "zxp rows: instruction %u stores at row shift %d", k,
+                                     (int)(int32_t)a.opnd[I.dst].c);
+                stored[a.opnd[I.dst].a] = true;
+            }
+        }
+        for (uint32_t s = 0; s < SEC_COUNT; s++)
+            if (read[s] && stored[s])
+                return set_error(ZKGPU_ERR_ARG, "zxp rows: section %u is both read and stored to", s);
+        for (uint32_t s = 0; s < SEC_COUNT; s++)
+            if (stored[s] && S.ld[s] < a.n_rows)
+                return set_error(ZKGPU_ERR_ARG, "zxp rows: section %u is stored to and holds %llu rows, not %u", s,
+                                 (unsigned long long)S.ld[s], a.n_rows);
+    }
     for (uint32_t k = 0; k < a.n_opnd; k++) {
         const zxp_operand &o = a.opnd[k];
         bool bad = false;
@@ -37,7 +68,9 @@ int zxp_validate(const ZxpArgs &a)
             // store (the reference's parser opcodes 101-114 / 119 write pols[off + ((i + s) % N) * stride],
             // step3.parser.cpp) lands on row (i + s) mod 2^log_dom, in a row block on local row i + s, the
             // last s of them in the halo rows, which the caller hands to the next block's owner
-            const uint64_t need = (1ULL << a.log_dom) + (a.wrap ? 0 : (uint64_t)(sh > 0 ? sh : 0));
+            const uint64_t need = o.a < SEC_COUNT && stored[o.a]
+                                      ? a.n_rows
+                                      : (1ULL << a.log_dom) + (a.wrap ? 0 : (uint64_t)(sh > 0 ? sh : 0));
             bad = o.a >= SEC_COUNT || !S.sec[o.a] || (uint64_t)o.b + w > S.ncols[o.a] || S.ld[o.a] < need ||
                   (!a.wrap && sh < 0);
             break;
@@ -140,7 +173,8 @@ int zxp_plan(const ZxpArgs &a, ZxpPlan &p)
     const int jit_mode = env_jit ? atoi(env_jit) : 1;
     // (the compiled kernels address a column with a 32-bit byte offset:
     // domains up to 2^28 rows plus their halo)
-    p.jit = fuse && a.log_dom <= 28 && (jit_mode == 2 || (jit_mode == 1 && a.log_dom >= 16));
+    // (a row list always runs on the interpreter: at most 4096 rows)
+    p.jit = !a.row_list && fuse && a.log_dom <= 28 && (jit_mode == 2 || (jit_mode == 1 && a.log_dom >= 16));
     int rc;
     if (fuse) {
         // (one compile serves both paths: measured, longer DOTs / fused DOT
@@ -175,7 +209,7 @@ int zxp_plan(const ZxpArgs &a, ZxpPlan &p)
         const uint32_t kind = a.opnd[k].kind;
         p.bytes += kind == ZXP_COL ? 1 : (kind == ZXP_COL3 || kind == ZXP_XDIV || kind == ZXP_XDIVW) ? 3 : 0;
     }
-    p.bytes *= 8.0 * (double)(1ULL << a.log_dom);
+    p.bytes *= 8.0 * (a.row_list ? (double)a.n_rows : (double)(1ULL << a.log_dom));
     return 0;
 }
 

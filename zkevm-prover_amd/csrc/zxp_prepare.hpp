@@ -71,7 +71,13 @@ struct ZxpArgs {
     const uint64_t *xdiv, *xdivw;  // device
     uint32_t extend_bits;
     uint64_t x_start;
+    // zkgpu_zxp_eval_rows_dev: the program runs at rows[0 .. n_rows) (device) of the domain and its
+    // stores are compact (index j of the destination for rows[j])
+    bool row_list = false;
+    const uint64_t *rows = nullptr;
+    uint32_t n_rows = 0;
 };
+constexpr uint32_t ZXP_MAX_LIST_ROWS = 4096;
 
 // What runs: the compiled program (its tables are the compiler's, valid on
 // this thread until its next compile), or with ZKGPU_ZXP_FUSE=0 the source

@@ -28,8 +28,9 @@
 //        PCIe under stage 1 of the proof, zkgpu_stark_prove_from_rows; single GPU)
 //        (--check-trace: the constraint check in its STOP mode, zkgpu_stark_check_set:
 //        a trace with a row that breaks the AIR ends the run before stage 3's
-//        commit with the first such row in the message, a non-zero status and
-//        no proof files; single GPU)
+//        commit with the first such row in the message and the terms of the
+//        constraint combination that fail there (zkgpu_stark_check_names_set),
+//        a non-zero status and no proof files; single GPU)
 //        (--shard: one rank of ONE proof row-sharded over WORLD processes,
 //        zkgpu_stark_create_sharded; every rank runs this command with the
 //        same config, rank 0 writes the outputs.  rccl: rank 0 writes the
@@ -261,6 +262,10 @@ static int prove(const std::string &config_path, const Shard &sh)
     }
     if (sh.check_trace && zkgpu_stark_check_set(h, ZKGPU_CHECK_STOP))
         throw std::runtime_error(std::string("--check-trace: ") + zkgpu_stark_last_error());
+    // the failing identities with the failing rows; a quotient program the split refuses: rows only
+    if (sh.check_trace && zkgpu_stark_check_names_set(h, 1))
+        fprintf(stderr, "--check-trace: %s; the failing rows will be named, not the identities\n",
+                zkgpu_stark_last_error());
     const auto t1 = clk::now();
     const uint64_t len = zkgpu_stark_proof_len(h);
     if (len != flat_len(info)) throw std::runtime_error("proof length mismatch");

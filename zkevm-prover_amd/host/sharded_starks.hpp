@@ -734,6 +734,10 @@ public:
         return fail("stark (sharded): check_set is single-GPU only (the n-domain sections live in row blocks on the "
                     "ranks)");
     }
+    int check_names_set(int) override
+    {
+        return fail("stark (sharded): check_names_set is single-GPU only (as check_set)");
+    }
     int prove_from_rows(const uint64_t *, int, uint64_t *) override
     {
         return fail("stark (sharded): prove_from_rows is single-GPU only (each rank loads its rows: set_cm1 / "

@@ -222,6 +222,7 @@ public:
         for (void *t : cm1_ticket) (void)zkgpu_load_wait(t);
         probe_clear();
         if (check_dev) (void)zkgpu_dev_free(check_dev);
+        if (names_dev) (void)zkgpu_dev_free(names_dev);
         for (void *p : allocs) zkgpu_dev_free(p);
     }
 
@@ -1248,17 +1249,39 @@ public:
         CK(zkgpu_nonzero_rows_dev(check_dev, c, N, 3, N, ZKGPU_CHECK_MAX_ROWS));
         // C at the first failing row (a row index past the domain -- none failed -- reads 0)
         CK(zkgpu_gather_rows_dev(check_dev + 1 + ZKGPU_CHECK_MAX_ROWS, c, N, 3, check_dev + 1, 1));
+        if (names_on) {
+            // every term of C at the listed rows: the tapped program over the same sections, its
+            // 3K output columns the names' block (ld 16), the row list the check's own on the device
+            T.sec[SEC_Q_2NS] = names_dev;
+            T.ld[SEC_Q_2NS] = ZKGPU_CHECK_MAX_ROWS;
+            T.ncols[SEC_Q_2NS] = 3 * (uint32_t)names_terms.size();
+            CK(zkgpu_zxp_eval_rows_dev(names_instr.data(), (uint32_t)names_instr.size(), names_opnd.data(),
+                                       (uint32_t)names_opnd.size(), step42ns.n_tmp1 ? step42ns.n_tmp1 : 1,
+                                       step42ns.n_tmp3 ? step42ns.n_tmp3 : 1, &T, info.n_bits, chk, publics.data(),
+                                       (uint32_t)publics.size(), ev0, 0, nullptr, nullptr, 0, 1, check_dev + 1,
+                                       ZKGPU_CHECK_MAX_ROWS));
+        }
         if (tstop("ZKGPU_CHECK_CONSTRAINTS")) return -1;
         if (check_mode == ZKGPU_CHECK_REPORT) {
             check_pending = true;
             return 0;
         }
         if (check_readback()) return -1;  // STOP: the one synchronisation
-        if (check_res.n_bad)
+        if (check_res.n_bad) {
+            // the terms that fail at the first row, up to 8 (with naming on)
+            std::string tail;
+            if (names_on) {
+                const std::vector<uint32_t> &ids = names_ids[0];
+                if (!ids.empty()) tail = "; failing terms there:";
+                for (size_t k = 0; k < ids.size() && k < 8; k++) tail += " " + std::to_string(ids[k]);
+                if (ids.size() > 8) tail += " and " + std::to_string(ids.size() - 8) + " more";
+                if (!ids.empty()) tail += " (zkgpu_stark_check_named)";
+            }
             return fail("constraint check: %llu of the 2^%u = %llu rows of the trace break the AIR; the first is row "
-                        "%llu (zkgpu_stark_check_result lists the lowest %u)",
+                        "%llu (zkgpu_stark_check_result lists the lowest %u)%s",
                         (unsigned long long)check_res.n_bad, info.n_bits, (unsigned long long)N,
-                        (unsigned long long)check_res.rows[0], (unsigned)ZKGPU_CHECK_MAX_ROWS);
+                        (unsigned long long)check_res.rows[0], (unsigned)ZKGPU_CHECK_MAX_ROWS, tail.c_str());
+        }
         return 0;
     }
     int check_readback()
@@ -1270,6 +1293,99 @@ public:
         for (int k = 0; k < 3; k++) check_res.value[k] = h[1 + ZKGPU_CHECK_MAX_ROWS + k] % P;
         check_res.ran = 1;
         check_pending = false;
+        for (auto &v : names_ids) v.clear();
+        for (auto &v : names_vals) v.clear();
+        names_ran = names_on;
+        if (names_on && check_res.n_bad) {
+            // the names' block: only with a failing row, only its first min(n_bad, 16) rows count
+            const size_t K = names_terms.size();
+            std::vector<uint64_t> b(3 * K * ZKGPU_CHECK_MAX_ROWS);
+            CK(zkgpu_memcpy_d2h(b.data(), names_dev, b.size() * 8));
+            const uint64_t n_listed = std::min<uint64_t>(check_res.n_bad, ZKGPU_CHECK_MAX_ROWS);
+            for (uint64_t j = 0; j < n_listed; j++)
+                for (size_t k = 0; k < K; k++) {
+                    if (names_terms[k].dead) continue;
+                    uint64_t v[3];
+                    for (int t = 0; t < 3; t++) v[t] = b[(3 * k + t) * ZKGPU_CHECK_MAX_ROWS + j] % P;
+                    if (!(v[0] | v[1] | v[2])) continue;
+                    names_ids[j].push_back((uint32_t)k);
+                    names_vals[j].insert(names_vals[j].end(), v, v + 3);
+                }
+        }
+        return 0;
+    }
+
+    // ---- naming (zkgpu_stark_check_names_set): which terms of C fail at the listed rows.
+    // zkgpu_zxp_split_constraints takes the n-domain step42ns apart once; the tapped program runs
+    // at the check's row list (zkgpu_zxp_eval_rows_dev) into a device block of 3K x 16 words of
+    // the names' own, outside the memory plan like the check's block.
+    bool names_on = false, names_ran = false;
+    std::vector<zxp_instr> names_instr;
+    std::vector<zxp_operand> names_opnd;
+    std::vector<zxp_split_term> names_terms;
+    uint64_t *names_dev = nullptr;
+    std::vector<uint32_t> names_ids[ZKGPU_CHECK_MAX_ROWS];
+    std::vector<uint64_t> names_vals[ZKGPU_CHECK_MAX_ROWS];
+
+    virtual int check_names_set(int on)
+    {
+        if (!on) {
+            names_on = false;
+            return 0;
+        }
+        if (names_terms.empty()) {
+            std::vector<zxp_operand> nd(step42ns.opnd.size() + 1);
+            if (zkgpu_zxp_to_n_domain(nd.data(), step42ns.instr.data(), (uint32_t)step42ns.instr.size(),
+                                      step42ns.opnd.data(), (uint32_t)step42ns.opnd.size(), eb)) {
+                names_on = false;
+                return fail("check_names_set: step42ns: %s; naming is off", zkgpu_last_error());
+            }
+            const size_t ni = step42ns.instr.size(), no = step42ns.opnd.size();
+            std::vector<zxp_instr> ti(2 * ni + 1);
+            std::vector<zxp_operand> to(no + 2 * ni + 1);
+            std::vector<zxp_split_term> tt(2 * ni + 1);
+            uint32_t n_i = 0, n_o = 0, n_t = 0;
+            if (zkgpu_zxp_split_constraints(ti.data(), &n_i, to.data(), &n_o, tt.data(), &n_t, step42ns.instr.data(),
+                                            (uint32_t)ni, nd.data(), (uint32_t)no, 4)) {
+                names_on = false;
+                return fail("check_names_set: step42ns: %s; naming is off", zkgpu_last_error());
+            }
+            ti.resize(n_i), to.resize(n_o), tt.resize(n_t);
+            names_instr.swap(ti), names_opnd.swap(to), names_terms.swap(tt);
+        }
+        if (!names_dev) {
+            void *v = nullptr;
+            if (zkgpu_dev_malloc(&v, 3 * names_terms.size() * ZKGPU_CHECK_MAX_ROWS * 8)) {
+                names_on = false;
+                return fail("check_names_set: %s; naming is off", zkgpu_last_error());
+            }
+            names_dev = (uint64_t *)v;
+        }
+        names_on = true;
+        return 0;
+    }
+    int check_terms(zxp_split_term *out, uint32_t max, uint32_t *n) const
+    {
+        if (!n) return fail("check_terms: null count");
+        *n = (uint32_t)names_terms.size();
+        if (names_terms.empty()) return fail("check_terms: naming has not been set on this prover");
+        if (max && !out) return fail("check_terms: null buffer");
+        for (uint32_t k = 0; k < max && k < names_terms.size(); k++) out[k] = names_terms[k];
+        return 0;
+    }
+    int check_named(uint32_t slot, uint32_t *ids, uint64_t *values, uint32_t max, uint32_t *n_failing) const
+    {
+        if (!n_failing) return fail("check_named: null count");
+        *n_failing = 0;
+        if (slot >= ZKGPU_CHECK_MAX_ROWS) return fail("check_named: slot %u of %u", slot, (unsigned)ZKGPU_CHECK_MAX_ROWS);
+        if (!check_res.ran || !names_ran) return fail("check_named: the last proof ran no check with naming on");
+        if (max && (!ids || !values)) return fail("check_named: null buffer");
+        const std::vector<uint32_t> &v = names_ids[slot];
+        *n_failing = (uint32_t)v.size();
+        for (uint32_t k = 0; k < max && k < v.size(); k++) {
+            ids[k] = v[k];
+            memcpy(values + 3 * k, names_vals[slot].data() + 3 * k, 24);
+        }
         return 0;
     }
     int check_result(zkgpu_check_result *out) const
@@ -1341,6 +1457,9 @@ public:
         probe_valid = false;
         check_pending = false;
         check_res = zkgpu_check_result{};
+        names_ran = false;
+        for (auto &v : names_ids) v.clear();
+        for (auto &v : names_vals) v.clear();
         timers.clear();
         pend_t.clear();
         pend_x.clear();
@@ -1791,6 +1910,15 @@ int zkgpu_stark_probe_set(void *h, const uint64_t *rows_n, uint32_t n_rows_n, co
 }
 int zkgpu_stark_check_set(void *h, uint32_t mode) { return ((Starks *)h)->check_set(mode); }
 int zkgpu_stark_check_result(void *h, zkgpu_check_result *out) { return ((Starks *)h)->check_result(out); }
+int zkgpu_stark_check_names_set(void *h, int on) { return ((Starks *)h)->check_names_set(on); }
+int zkgpu_stark_check_terms(void *h, zxp_split_term *out, uint32_t max, uint32_t *n)
+{
+    return ((Starks *)h)->check_terms(out, max, n);
+}
+int zkgpu_stark_check_named(void *h, uint32_t slot, uint32_t *ids, uint64_t *values, uint32_t max, uint32_t *n_failing)
+{
+    return ((Starks *)h)->check_named(slot, ids, values, max, n_failing);
+}
 int zkgpu_stark_probe_size(void *h, uint32_t *n_recs, uint64_t *n_words)
 {
     return ((Starks *)h)->probe_size(n_recs, n_words);

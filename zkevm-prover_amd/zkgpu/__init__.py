@@ -97,6 +97,9 @@ _SIGS = {
     "zkgpu_lde_workspace_bytes": (u64, [u64, u64, u64]),
     "zkgpu_zxp_eval_dev": (ctypes.c_int, [vp, u32, vp, u32, u32, u32, vp, u32, vp, vp, u32, vp, u32, vp, vp, u32,
                                           u64]),
+    "zkgpu_zxp_eval_rows_dev": (ctypes.c_int, [vp, u32, vp, u32, u32, u32, vp, u32, vp, vp, u32, vp, u32, vp, vp, u32,
+                                               u64, vp, u32]),
+    "zkgpu_zxp_split_constraints": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, u32]),
     "zkgpu_zxp_compile": (ctypes.c_int, [vp, u32, vp, u32, u32, u32, vp, vp, u32, vp, u32, u32, vp]),
     "zkgpu_zxp_jit_source": (ctypes.c_int, [vp, u32, vp, u32, u32, u32, vp, vp, u32, vp, u32, vp, u64,
                                             ctypes.c_int]),
@@ -431,6 +434,26 @@ def zxp_to_n_domain(ins, opn, extend_bits):
     return out[:opn.shape[0]]
 
 
+def zxp_split_constraints(ins, opn, chal=4):
+    """The constraint combination of a quotient program taken apart
+    (zkgpu_zxp_split_constraints, no GPU needed) -> (tapped instructions,
+    tapped operands, terms): terms is an (n_terms, 4) uint32 array of
+    (exponent, negated, instr, dead); term k's value is what the tapped program
+    stores to COL3(SEC_Q_2NS, 3k)"""
+    ins = np.ascontiguousarray(ins, np.uint32).reshape(-1, 4)
+    opn = np.ascontiguousarray(opn, np.uint32).reshape(-1, 4)
+    n = ins.shape[0]
+    ins_out = np.zeros((max(2 * n, 1), 4), np.uint32)
+    opn_out = np.zeros((opn.shape[0] + 2 * n + 1, 4), np.uint32)
+    terms = np.zeros((max(2 * n, 1), 4), np.uint32)
+    cnt = np.zeros(3, np.uint32)
+    _check(lib().zkgpu_zxp_split_constraints(ins_out.ctypes.data, cnt[0:].ctypes.data, opn_out.ctypes.data,
+                                             cnt[1:].ctypes.data, terms.ctypes.data, cnt[2:].ctypes.data,
+                                             ins.ctypes.data, n, opn.ctypes.data, opn.shape[0], chal),
+           "zkgpu_zxp_split_constraints")
+    return ins_out[:cnt[0]].copy(), opn_out[:cnt[1]].copy(), terms[:cnt[2]].copy()
+
+
 def rows_to_cols_dev(cols, ld, rows, nrows, ncols):
     _check(lib().zkgpu_rows_to_cols_dev(_addr(cols), ld, _addr(rows), nrows, ncols), "zkgpu_rows_to_cols_dev")
 
@@ -635,6 +658,37 @@ def zxp_eval_dev(prog, sections, log_dom, challenges, publics, evals=None, xdiv=
                                     max(nt3, 1), ctypes.byref(s), log_dom, ch.ctypes.data, pub.ctypes.data,
                                     pub.size if publics is not None else 0, ev.ctypes.data, ev.size // 3,
                                     _addr(xdiv), _addr(xdivw), extend_bits, x_start), "zkgpu_zxp_eval_dev")
+
+
+def zxp_eval_rows_dev(prog, sections, log_dom, challenges, publics, rows, n_rows, evals=None, xdiv=None, xdivw=None,
+                      extend_bits=0, x_start=1):
+    """zxp_eval_dev at the rows rows[0 .. n_rows) (a device tensor of row
+    indices; an entry >= 2^log_dom is skipped): reads come from the whole
+    sections, a store goes to index j of its column for rows[j]
+    (zkgpu_zxp_eval_rows_dev; queued on the library stream, no host
+    synchronisation)"""
+    if hasattr(prog, "arrays"):
+        ins, opn = prog.arrays()
+        nt1, nt3 = prog.n_tmp1, prog.n_tmp3
+    else:
+        ins, opn, nt1, nt3 = prog
+    ins = np.ascontiguousarray(ins, np.uint32)
+    opn = np.ascontiguousarray(opn, np.uint32)
+    s = Sections()
+    for k, (t, ld, nc) in sections.items():
+        s.sec[k] = _addr(t)
+        s.ld[k] = ld
+        s.ncols[k] = nc
+    ch = np.zeros(24, np.uint64)
+    c = _np(challenges).reshape(-1)
+    ch[:c.size] = c
+    pub = _np(publics if publics is not None else np.zeros(1, np.uint64))
+    ev = _np(evals if evals is not None else np.zeros(3, np.uint64)).reshape(-1)
+    _check(lib().zkgpu_zxp_eval_rows_dev(ins.ctypes.data, ins.shape[0], opn.ctypes.data, opn.shape[0], max(nt1, 1),
+                                         max(nt3, 1), ctypes.byref(s), log_dom, ch.ctypes.data, pub.ctypes.data,
+                                         pub.size if publics is not None else 0, ev.ctypes.data, ev.size // 3,
+                                         _addr(xdiv), _addr(xdivw), extend_bits, x_start, _addr(rows), n_rows),
+           "zkgpu_zxp_eval_rows_dev")
 
 
 class ZxpCompiled(ctypes.Structure):

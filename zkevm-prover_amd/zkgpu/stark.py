@@ -97,6 +97,9 @@ def slib():
             ("zkgpu_stark_probe_read", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp, u64]),
             ("zkgpu_stark_check_set", ctypes.c_int, [vp, ctypes.c_uint32]),
             ("zkgpu_stark_check_result", ctypes.c_int, [vp, ctypes.POINTER(CheckResult)]),
+            ("zkgpu_stark_check_names_set", ctypes.c_int, [vp, ctypes.c_int]),
+            ("zkgpu_stark_check_terms", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp]),
+            ("zkgpu_stark_check_named", ctypes.c_int, [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp]),
             ("zkgpu_stark_create_sharded", ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(_Info),
                                                           ctypes.POINTER(Comm)]),
             ("zkgpu_stark_memory_plan", ctypes.c_int, [ctypes.POINTER(_Info), ctypes.c_uint32,
@@ -461,6 +464,38 @@ class GpuStark:
         rows = [int(x) for x in r.rows if x != 2**64 - 1]
         return {"ran": int(r.ran), "n_bad": int(r.n_bad), "rows": rows, "value": [int(x) for x in r.value],
                 "alpha": [int(x) for x in r.alpha]}
+
+    def check_names_set(self, on=True):
+        """naming of every later checked proof (zkgpu_stark_check_names_set):
+        the terms of the constraint combination that fail at the listed rows"""
+        _check(slib().zkgpu_stark_check_names_set(self.h, 1 if on else 0), "zkgpu_stark_check_names_set")
+
+    def check_terms(self):
+        """the term table (n_terms, 4) uint32: exponent, negated, instr, dead
+        (zkgpu_stark_check_terms; instr: the step42ns instruction at which the
+        term -- the k-th identity folded -- joined the combination)"""
+        n = ctypes.c_uint32(0)
+        _check(slib().zkgpu_stark_check_terms(self.h, None, 0, ctypes.byref(n)), "zkgpu_stark_check_terms")
+        out = np.zeros((n.value, 4), np.uint32)
+        _check(slib().zkgpu_stark_check_terms(self.h, out.ctypes.data, n.value, ctypes.byref(n)),
+               "zkgpu_stark_check_terms")
+        return out
+
+    def check_named(self, slot, max_terms=None):
+        """the live terms that are not zero at the failing row rows[slot] of
+        the last checked proof -> (ids ascending, their values as 3 ints each,
+        their total number); max_terms: at most that many are returned"""
+        n = ctypes.c_uint32(0)
+        if max_terms is None:
+            _check(slib().zkgpu_stark_check_named(self.h, slot, None, None, 0, ctypes.byref(n)),
+                   "zkgpu_stark_check_named")
+            max_terms = n.value
+        ids = np.zeros(max(max_terms, 1), np.uint32)
+        vals = np.zeros((max(max_terms, 1), 3), np.uint64)
+        _check(slib().zkgpu_stark_check_named(self.h, slot, ids.ctypes.data, vals.ctypes.data, max_terms,
+                                              ctypes.byref(n)), "zkgpu_stark_check_named")
+        k = min(max_terms, n.value)
+        return [int(x) for x in ids[:k]], [[int(x) for x in v] for v in vals[:k]], int(n.value)
 
     def timers(self):
         names = ctypes.create_string_buffer(4096)
