@@ -560,7 +560,11 @@ int zkgpu_gl_field_selftest_dev(uint64_t *out, const uint64_t *a, const uint64_t
  * 3 gl_reduce128_rb(lo = a, hi = b), 4 gl_reduce96_small_rb(lo = a, hl = b mod 2^32),
  * 5 dot3_fin_rb(A0 = a, A1 = b, A2 = c), 6 mul2e_rb<e>(a), 7 mul2e<e>(a) (0 <= e < 192),
  * 8 the Poseidon S-box a^7 (pow7), 9 its squaring gl_sqr3(a),
- * 10 gl_reduce128(lo = a, hi = b), 11 Dot3::fin(A0 = a, A1 = b, A2 = c).
+ * 10 gl_reduce128(lo = a, hi = b), 11 Dot3::fin(A0 = a, A1 = b, A2 = c),
+ * 12 Dot2::fin(L = a, H = b), the two-accumulator reduction of the Poseidon
+ * power blocks (a + 2^32 b; the kernels keep both below 2^58, the reduction is
+ * exact for any a and any b < 2^63; it has no rare-branch variant: its
+ * correction is common).
  * Canonical results; c is read by ops 5 and 11 only. */
 int zkgpu_gl_field_selftest_rb_dev(uint64_t *out, const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t n,
                                    int op, int e);

@@ -264,7 +264,175 @@ def perm_blocks(st, rc, pre, d0, blocks):
     return st
 
 
-def emit(path, pre, post, D0, W, V, d0tab=None, btabs=None, cap0=None):
+# ---------------------------------------------------------------- power blocks
+# Partial rounds as blocks of up to three TEXTBOOK rounds over the original
+# lanes.  With s the lanes at block start (the block's first round constants
+# already added), Z = diag(0, 1, .., 1) and y_i the S-box output of round i:
+#     s_y = s with lane 0 replaced by y0 = s[0]^7
+#     u1 = (P1 s_y)[0] + K1                               y1 = u1^7
+#     u2 = (P2 s_y)[0] + P1[0][0] y1 + K2                 y2 = u2^7
+#     s' = P3 s_y + (P2 e0) y1 + (P1 e0) y2 + K3
+#     P1 = M,  P2 = M Z M,  P3 = M Z M Z M
+# Z drops the lane-0 value that the next S-box replaces, so the S-box outputs
+# enter as themselves (no u^7 - u differences, no subtraction) and every
+# coefficient is a non-negative integer <= the matching entry of M, M^2, M^3
+# (< 2^21): a lane's 32-bit halves times a coefficient sum carry-free in two
+# u64 accumulators.  A block of n < 3 rounds stops at P_n.
+POW_SCHEDULES = {"7x3+1": [3] * 7 + [1], "6x3+2x2": [3] * 6 + [2, 2]}
+POW_SCHEDULE = "7x3+1"  # the device code's (csrc/poseidon_perm.hpp partial_rounds_pow3)
+
+
+def pow_mats():
+    """[P1, P2, P3] as plain integers (never reduced: they stay < 2^21)."""
+    M = mds()
+
+    def zmul(a, b):  # a Z b
+        return [[sum(a[i][t] * b[t][j] for t in range(1, 12)) for j in range(12)] for i in range(12)]
+
+    P1 = M
+    P2 = zmul(M, P1)
+    P3 = zmul(M, P2)
+    return [P1, P2, P3]
+
+
+def pow_block_rows(n):
+    """The dot products of an n-round block, in evaluation order: (kind, row, coefficients) with
+    kind 'u' (the next S-box input, row 0 of P_i) or 's' (output lane `row`); the coefficients
+    multiply s_y[0..11], then y1 .. (as many as are known)."""
+    Pm = pow_mats()
+    rows = []
+    for i in range(1, n):
+        rows.append(("u", i, Pm[i - 1][0] + [Pm[i - m - 1][0][0] for m in range(1, i)]))
+    for x in range(12):
+        rows.append(("s", x, Pm[n - 1][x] + [Pm[n - m - 1][x][0] for m in range(1, n)]))
+    return rows
+
+
+def pow_acc_bound(n):
+    """Largest value either u64 accumulator of an n-round block can reach for arbitrary u64
+    lanes and S-box outputs: the 32-bit seed plus (2^32 - 1) times the row's coefficient sum."""
+    return max((1 << 32) - 1 + ((1 << 32) - 1) * sum(c) for _, _, c in pow_block_rows(n))
+
+
+def derive_pow_blocks(rc, schedule, pre=None):
+    """Per-block constants of the power-block form for a schedule (block lengths summing to RP).
+
+    The first block's input carries PRE (what the fourth full round's linear layer adds
+    today), not the plain round-4 constants: PRE - c_4 is a constant vector whose lane 0 is
+    zero, and its image under P1, P2, P3 is taken out of the first block's constants.  Every
+    block's last constant vector holds the next round's constants, the last block's the
+    round-26 ones.  Returns a list of blocks, each a list of u32: for i < n the low and high
+    half of K_i, then the 12 (low, high) pairs of the vector K_n -- the seeds of the two
+    accumulators of each dot product."""
+    assert sum(schedule) == RP and all(1 <= n <= 3 for n in schedule)
+    if pre is None:
+        pre = derive(rc)[0]
+    M = mds()
+    c4 = rc[RF_HALF * 12:(RF_HALF + 1) * 12]
+    assert pre[0] == c4[0]
+    k = [0] + [(c4[i] - pre[i]) % P for i in range(1, 12)]  # true lanes = given lanes + k
+    out = []
+    r = RF_HALF
+    for n in schedule:
+        assert pow_acc_bound(n) < 1 << 64
+        words = []
+        for i in range(1, n + 1):
+            full = [(v + c) % P for v, c in zip(matvec(M, k), rc[(r + i) * 12:(r + i + 1) * 12])]
+            if i < n:
+                words += [full[0] & 0xFFFFFFFF, full[0] >> 32]
+                k = [0] + full[1:]
+            else:
+                for v in full:
+                    words += [v & 0xFFFFFFFF, v >> 32]
+        k = [0] * 12
+        r += n
+        out.append(words)
+    return out
+
+
+def pow_block_eval(s, words, n, check=None):
+    """One n-round block exactly as the device evaluates it: integer accumulators, reduced
+    once per dot product.  s: any u64 lanes.  check(lo, hi) sees every accumulator pair."""
+    y = [pow(s[0], 7, P)]
+    sy = [y[0]] + list(s[1:])
+    pos = 0
+    res = []
+    for kind, _, coef in pow_block_rows(n):
+        vals = sy + y[1:]
+        assert len(vals) == len(coef)
+        lo = words[pos] + sum((v & 0xFFFFFFFF) * c for v, c in zip(vals, coef))
+        hi = words[pos + 1] + sum((v >> 32) * c for v, c in zip(vals, coef))
+        pos += 2
+        if check:
+            check(lo, hi)
+        v = (lo + (hi << 32)) % P
+        if kind == "u":
+            y.append(pow(v, 7, P))
+        else:
+            res.append(v)
+    assert pos == len(words)
+    return res
+
+
+def perm_pow_blocks(st, rc, pre, schedule, ktab, check=None):
+    """The permutation with the partial rounds in power-block form (tables only)."""
+    M = mds()
+    st = [(s + rc[i]) % P for i, s in enumerate(st)]
+    for r in range(RF_HALF):
+        st = [pow(s, 7, P) for s in st]
+        st = matvec(M, st)
+        nxt = rc[(r + 1) * 12:(r + 2) * 12] if r < RF_HALF - 1 else pre
+        st = [(s + c) % P for s, c in zip(st, nxt)]
+    for n, words in zip(schedule, ktab):
+        st = pow_block_eval(st, words, n, check)
+    for r in range(RF_HALF + RP, 2 * RF_HALF + RP):
+        st = [pow(s, 7, P) for s in st]
+        st = matvec(M, st)
+        if r < 2 * RF_HALF + RP - 1:
+            st = [(s + c) % P for s, c in zip(st, rc[(r + 1) * 12:(r + 2) * 12])]
+    return st
+
+
+def emit_pow(rc, pre):
+    """Header lines of the device schedule: the three-round blocks' seeds and the constants of
+    the single round left over (the plain round-26 constants: it is one textbook round)."""
+    sched = POW_SCHEDULES[POW_SCHEDULE]
+    assert sched[:-1] == [3] * (len(sched) - 1) and sched[-1] == 1
+    ktab = derive_pow_blocks(rc, sched, pre)
+    tail = [lo | (hi << 32) for lo, hi in zip(ktab[-1][0::2], ktab[-1][1::2])]
+    assert tail == rc[(RF_HALF + RP) * 12:(RF_HALF + RP + 1) * 12]
+    flat = [w for t in ktab[:-1] for w in t]
+    lines = ["// power-block form (see derive_pow_blocks), schedule %s: per three-round block the" % POW_SCHEDULE,
+             "// accumulator seeds K1, K2 (low, high half) and K3[0..11] (low, high pairs), u32",
+             f"#define ZKGPU_PSB3_NBLOCKS {len(ktab) - 1}",
+             f"#define ZKGPU_PSB3_BLOCK_WORDS {len(ktab[0])}",
+             f"static constexpr uint32_t ZKGPU_PSB3_K[{len(flat)}] = {{"]
+    for i in range(0, len(flat), 8):
+        lines.append("    " + ", ".join(f"0x{v:08x}u" for v in flat[i:i + 8]) + ",")
+    lines.append("};")
+    return lines
+
+
+def emit_pow_alt(path, rc, pre):
+    """The other schedule's seeds, for the isolated benchmark's variant only
+    (tools/poseidon_bench.hip): six three-round blocks, then two two-round blocks."""
+    sched = POW_SCHEDULES["6x3+2x2"]
+    ktab = derive_pow_blocks(rc, sched, pre)
+    lines = ["// GENERATED by tools/gen_poseidon_sparse.py -- do not edit.",
+             "// Power-block seeds of the 6x3+2x2 schedule (benchmark variant; the kernels use",
+             "// csrc/poseidon_gl_sparse.h ZKGPU_PSB3_K).  Per block: K_i (low, high) for i < n, then K_n[0..11].",
+             "#pragma once", "#include <stdint.h>"]
+    for name, n in (("PSB_ALT_K3", 3), ("PSB_ALT_K2", 2)):
+        flat = [w for nn, t in zip(sched, ktab) if nn == n for w in t]
+        lines.append(f"static constexpr uint32_t {name}[{len(flat)}] = {{")
+        for i in range(0, len(flat), 8):
+            lines.append("    " + ", ".join(f"0x{v:08x}u" for v in flat[i:i + 8]) + ",")
+        lines.append("};")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def emit(path, pre, post, D0, W, V, d0tab=None, btabs=None, cap0=None, pow_lines=None):
     def arr(name, vals, per=4):
         out = [f"static constexpr uint64_t {name}[{len(vals)}] = {{"]
         for i in range(0, len(vals), per):
@@ -308,6 +476,8 @@ def emit(path, pre, post, D0, W, V, d0tab=None, btabs=None, cap0=None):
                   "// (0 + RC[8 + k])^7 through the linear layer, plus the round-1 constants:",
                   "// K[x] = RC[12 + x] + sum_k M[x][8 + k] RC[8 + k]^7"]
         lines += arr("ZKGPU_PS_CAP0_K", cap0)
+    if pow_lines is not None:
+        lines += pow_lines
     lines += ["#endif  // ZKGPU_POSEIDON_GL_SPARSE_H", ""]
     with open(path, "w") as f:
         f.write("\n".join(lines))
@@ -337,8 +507,18 @@ def main():
         r0 = [pow((s + c) % P, 7, P) for s, c in zip(st, rc[:12])]
         full = [(v + c) % P for v, c in zip(matvec(M, r0), rc[12:24])]
         assert full == [(v + c) % P for v, c in zip(matvec(M, r0[:8] + [0] * 4), cap0)]
-    emit(os.path.join(ROOT, "zkevm-prover_amd/csrc/poseidon_gl_sparse.h"), pre, post, D0, W, V, d0tab, btabs, cap0)
-    print("sparse and block forms verified on random states; header written")
+    # power blocks: both schedules against the textbook form, every accumulator below 2^64
+    def below_2_64(lo, hi):
+        assert lo < 1 << 64 and hi < 1 << 64
+    for sched in POW_SCHEDULES.values():
+        ktab = derive_pow_blocks(rc, sched, pre)
+        for _ in range(16):
+            st = [rnd.randrange(P) for _ in range(12)]
+            assert perm_pow_blocks(st, rc, pre, sched, ktab, below_2_64) == perm_textbook(st, rc)
+    emit(os.path.join(ROOT, "zkevm-prover_amd/csrc/poseidon_gl_sparse.h"), pre, post, D0, W, V, d0tab, btabs, cap0,
+         emit_pow(rc, pre))
+    emit_pow_alt(os.path.join(ROOT, "tools/poseidon_bench_alt.h"), rc, pre)
+    print("sparse, block and power-block forms verified on random states; header written")
 
 
 if __name__ == "__main__":

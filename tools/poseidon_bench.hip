@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "../zkevm-prover_amd/csrc/poseidon_perm.hpp"
+#include "poseidon_bench_alt.h"
 
 using namespace zk;
 
@@ -75,6 +76,54 @@ __device__ __forceinline__ void perm_fast_v1(uint64_t st[12])
     full_rounds_fold_v1(st, 26);
 }
 
+// The generator's other schedule for the partial rounds, 6 three-round blocks
+// and 2 two-round blocks (poseidon_bench_alt.h), with a block body for any
+// length: an n-round block stops at P_n (csrc/poseidon_perm.hpp has n = 3).
+template <int N>
+__device__ __forceinline__ void psb_block_n(uint64_t st[12], const uint32_t *K)
+{
+    static_assert(N == 2 || N == 3, "block length");
+    st[0] = pow7(st[0]);
+    Dot2 d1(K[0], K[1]);
+#pragma unroll
+    for (int j = 0; j < 12; j++) d1.term(st[j], (uint32_t)ZKGPU_PSB3_P1.v[0][j]);
+    const uint64_t y1 = pow7(d1.fin());
+    uint64_t y2 = 0;
+    if constexpr (N == 3) {
+        Dot2 d2(K[2], K[3]);
+#pragma unroll
+        for (int j = 0; j < 12; j++) d2.term(st[j], (uint32_t)ZKGPU_PSB3_P2.v[0][j]);
+        d2.term(y1, (uint32_t)ZKGPU_PSB3_P1.v[0][0]);
+        y2 = pow7(d2.fin());
+    }
+    uint64_t out[12];
+#pragma unroll
+    for (int x = 0; x < 12; x++) {
+        Dot2 d(K[2 * (N - 1) + 2 * x], K[2 * (N - 1) + 2 * x + 1]);
+        if constexpr (N == 3) {
+#pragma unroll
+            for (int j = 0; j < 12; j++) d.term(st[j], (uint32_t)ZKGPU_PSB3_P3.v[x][j]);
+            d.term(y1, (uint32_t)ZKGPU_PSB3_P2.v[x][0]);
+            d.term(y2, (uint32_t)ZKGPU_PSB3_P1.v[x][0]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 12; j++) d.term(st[j], (uint32_t)ZKGPU_PSB3_P2.v[x][j]);
+            d.term(y1, (uint32_t)ZKGPU_PSB3_P1.v[x][0]);
+        }
+        out[x] = d.fin();
+    }
+#pragma unroll
+    for (int x = 0; x < 12; x++) st[x] = out[x];
+}
+
+__device__ __forceinline__ void partial_rounds_pow_6x3_2x2(uint64_t st[12])
+{
+#pragma unroll 1
+    for (int b = 0; b < 6; b++) psb_block_n<3>(st, &PSB_ALT_K3[b * 28]);
+#pragma unroll 1
+    for (int b = 0; b < 2; b++) psb_block_n<2>(st, &PSB_ALT_K2[b * 26]);
+}
+
 template <int V>
 __global__ void __launch_bounds__(256) k_perm(uint64_t *st_all, uint64_t n, int reps)
 {
@@ -95,7 +144,30 @@ __global__ void __launch_bounds__(256) k_perm(uint64_t *st_all, uint64_t n, int 
             full_rounds_fold(st, 0, 4);
             full_rounds_fold(st, 26, 4);
         }
-        if constexpr (V == 8) partial_rounds_blocks(st);  // the 22 partial rounds only
+        if constexpr (V == 8) partial_rounds_blocks(st);  // the 22 partial rounds only, 11-round sparse blocks
+        if constexpr (V == 9) partial_rounds_pow3(st);    // ... as three-round power blocks
+        if constexpr (V == 10) {  // the permutation with the 11-round sparse blocks
+#pragma unroll
+            for (int s = 0; s < 12; s++) st[s] = gl_add(st[s], ZKGPU_POSEIDON_RC[s]);
+            full_rounds_fold(st, 0, 4);
+            partial_rounds_blocks(st);
+            full_rounds_fold(st, 26, 4);
+        }
+        if constexpr (V == 12) partial_rounds_pow_6x3_2x2(st);  // the 22 partial rounds only, 6x3 + 2x2
+        if constexpr (V == 13) {  // the permutation with the 6x3 + 2x2 power blocks
+#pragma unroll
+            for (int s = 0; s < 12; s++) st[s] = gl_add(st[s], ZKGPU_POSEIDON_RC[s]);
+            full_rounds_fold(st, 0, 4);
+            partial_rounds_pow_6x3_2x2(st);
+            full_rounds_fold(st, 26, 4);
+        }
+        if constexpr (V == 11) {  // ... with the three-round power blocks
+#pragma unroll
+            for (int s = 0; s < 12; s++) st[s] = gl_add(st[s], ZKGPU_POSEIDON_RC[s]);
+            full_rounds_fold(st, 0, 4);
+            partial_rounds_pow3(st);
+            full_rounds_fold(st, 26, 4);
+        }
     }
 #pragma unroll
     for (int k = 0; k < 12; k++) st_all[k * n + i] = gl_canon(st[k]);
@@ -213,6 +285,7 @@ int main()
     const uint64_t n = 3 << 20;  // divisible by 2 and 3
     const int reps = 8;
     uint64_t *h = (uint64_t *)malloc(12 * n * 8), *ref = (uint64_t *)malloc(12 * n * 8), *o = (uint64_t *)malloc(12 * n * 8);
+    uint64_t *pref = (uint64_t *)malloc(12 * n * 8);  // the sparse-block partial rounds' states
     uint64_t x = 0x5EED;
     for (uint64_t i = 0; i < 12 * n; i++) {
         x ^= x << 13; x ^= x >> 7; x ^= x << 17;
@@ -232,6 +305,9 @@ int main()
         {"sparse/halves", k_perm<2>},
         {"sparse/limbs24", k_perm<3>},
         {"fast (FFT MDS + block dots)", k_perm<4>},
+        {"fast, 11-round sparse blocks", k_perm<10>},
+        {"fast, 3-round power blocks", k_perm<11>},
+        {"fast, power blocks 6x3 + 2x2", k_perm<13>},
         {"fast, multiply-add MDS (mds_fold)", k_perm<5>},
         {"fast, older MDS form", k_perm<6>},
         {"fast, K=1 generic (perm_fast_k)", k_permK<1>},
@@ -242,12 +318,14 @@ int main()
         {"fast, 7 waves/SIMD target", k_perm_w<7>},
         {"fast, 8 waves/SIMD target", k_perm_w<8>},
         {"split: 8 full rounds only", k_perm<7>},
-        {"split: 22 partial rounds only", k_perm<8>},
+        {"split: 22 partial, sparse blocks", k_perm<8>},
+        {"split: 22 partial, power blocks", k_perm<9>},
+        {"split: 22 partial, power 6x3+2x2", k_perm<12>},
         {"fast, tables by scalar loads", k_perm_smem},
         {"fast, tables in LDS", k_perm_lds},
         {"fast, scalar loads, opaque table", k_perm_smem2},
     };
-    const int nthreads_div[] = {1, 1, 1, 1, 1, 1, 1, 1, 2, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1};
+    const int nthreads_div[] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
     int bad = 0;
     const int nv = sizeof(ks) / sizeof(ks[0]);
     for (int v = 0; v < nv; v++) {
@@ -263,7 +341,12 @@ int main()
             if (ms < best) best = ms;
         }
         (void)hipMemcpy(v ? o : ref, d, 12 * n * 8, hipMemcpyDeviceToHost);
-        bool same = v == 0 || v == 14 || v == 15 || memcmp(o, ref, 12 * n * 8) == 0;
+        // the timing splits are not permutations: the two partial-round forms must agree with each other
+        const bool split = strncmp(ks[v].name, "split:", 6) == 0;
+        const bool first_partial = strcmp(ks[v].name, "split: 22 partial, sparse blocks") == 0;
+        if (first_partial) memcpy(pref, o, 12 * n * 8);
+        bool same = v == 0 || (split && !strstr(ks[v].name, "power")) ||
+                    memcmp(o, split ? pref : ref, 12 * n * 8) == 0;
         bad |= !same;
         printf("%-34s %8.3f ms  %7.2f Gperm/s  %s\n", ks[v].name, best, (double)n * reps / (best * 1e-3) / 1e9,
                same ? "match" : "MISMATCH");

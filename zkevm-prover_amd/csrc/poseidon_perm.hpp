@@ -1,12 +1,23 @@
 // Poseidon-GL permutation (t = 12, RF = 8, RP = 22, x^7) for gfx950 device code.
 //
-// Two exact evaluations of the reference's permutation
+// Exact evaluations of the reference's permutation
 // (poseidon_g_executor.cpp:201-231; PoseidonGoldilocks::hash_full_result):
 //
 //  * perm_textbook: every round = add constants, S-box, 12x12 MDS.
 //  * perm_sparse:   full rounds as above; the 22 partial rounds in the sparse
 //    form of tools/gen_poseidon_sparse.py (one dense 11x11 matrix, then per
 //    round 22 products instead of a 12x12 MDS).  Same output bit for bit.
+//  * perm_fast (the kernels' form): full rounds with the constants folded
+//    into a frequency-domain MDS; the partial rounds as seven blocks of three
+//    textbook rounds over the original lanes plus one single round
+//    (partial_rounds_pow3).  Inside a block the linear layers between the
+//    lane-0 S-boxes are multiplied out: the matrices P1 = M, P2 = M Z M,
+//    P3 = M Z M Z M (Z drops lane 0, which the next S-box replaces) have plain
+//    integer entries below 2^21, so a dot-product term is two multiply-adds
+//    of a lane's 32-bit halves into two carry-free u64 accumulators.
+//    ZKGPU_PSB_POW3=0 selects the earlier form, the sparse factorisation
+//    regrouped into two 11-round blocks with 64-bit table coefficients
+//    (partial_rounds_blocks, six multiply-adds per term).
 //
 // MDS (full rounds): the entries are < 64 and each row sums to < 2^9, so each
 // lane is split into 22/22/20-bit limbs and every limb's dot product is
@@ -444,12 +455,150 @@ __device__ __forceinline__ void partial_rounds_blocks(uint64_t st[12], TP D0 = Z
     for (int j = 0; j < 11; j++) st[1 + j] = L[j];
 }
 
+// ---------------------------------------------------------- power blocks
+// Partial rounds as blocks of three TEXTBOOK rounds over the original lanes
+// (tools/gen_poseidon_sparse.py derive_pow_blocks has the algebra): with
+// Z = diag(0, 1, .., 1) and s_y = the lanes with lane 0 replaced by its S-box
+// output y0,
+//     u1 = (P1 s_y)[0] + K1                      y1 = u1^7
+//     u2 = (P2 s_y)[0] + P1[0][0] y1 + K2        y2 = u2^7
+//     s' = P3 s_y + (P2 e0) y1 + (P1 e0) y2 + K3
+//     P1 = M,  P2 = M Z M,  P3 = M Z M Z M
+// Every coefficient is a plain integer < 2^21 (no 64-bit field coefficients):
+// a term is two multiply-adds, a lane's 32-bit halves times the coefficient
+// into a low and a high u64 accumulator, against six for a Dot3 term.
+struct PsbMat {
+    uint64_t v[12][12];
+};
+__host__ __device__ constexpr PsbMat psb3_p1()
+{
+    PsbMat m{};
+    for (int x = 0; x < 12; x++)
+        for (int y = 0; y < 12; y++) m.v[x][y] = mds_entry(x, y);
+    return m;
+}
+// a Z b
+__host__ __device__ constexpr PsbMat psb3_zmul(const PsbMat &a, const PsbMat &b)
+{
+    PsbMat m{};
+    for (int x = 0; x < 12; x++)
+        for (int y = 0; y < 12; y++)
+            for (int t = 1; t < 12; t++) m.v[x][y] += a.v[x][t] * b.v[t][y];
+    return m;
+}
+static constexpr PsbMat ZKGPU_PSB3_P1 = psb3_p1();
+static constexpr PsbMat ZKGPU_PSB3_P2 = psb3_zmul(ZKGPU_PSB3_P1, ZKGPU_PSB3_P1);
+static constexpr PsbMat ZKGPU_PSB3_P3 = psb3_zmul(ZKGPU_PSB3_P1, ZKGPU_PSB3_P2);
+// largest coefficient sum of a dot product: a row of P3 and its y1, y2 terms
+__host__ __device__ constexpr uint64_t psb3_max_rowsum()
+{
+    uint64_t best = 0;
+    for (int x = 0; x < 12; x++) {
+        uint64_t s = ZKGPU_PSB3_P2.v[x][0] + ZKGPU_PSB3_P1.v[x][0];
+        for (int y = 0; y < 12; y++) s += ZKGPU_PSB3_P3.v[x][y];
+        best = s > best ? s : best;
+    }
+    return best;
+}
+// either accumulator: a 32-bit seed plus (2^32 - 1) * (coefficient sum) < 2^58,
+// for ANY u64 lanes (the generator asserts the same from its own integers)
+static_assert(psb3_max_rowsum() < (1ull << 25), "power-block accumulators must stay carry-free");
+
+// Dot product of lazy lanes with small integer coefficients: value =
+// L + 2^32 H, both < 2^58, so the sum is below 2^90 and the word above 2^64
+// is < 2^27.
+struct Dot2 {
+    uint64_t L, H;
+    __device__ __forceinline__ Dot2(uint32_t kl, uint32_t kh) : L(kl), H(kh) {}
+    __device__ __forceinline__ void term(uint64_t a, uint32_t c)
+    {
+        L += (uint64_t)(uint32_t)a * c;
+        H += (uint64_t)(uint32_t)(a >> 32) * c;
+    }
+    // One lazy word.  Select form: with h up to 2^27 the carry of lo + h EPS
+    // needs lo >= 2^64 - 2^59, about one lane in 32 -- most waves would take
+    // a wave-uniform branch, so there is no rare-branch variant.  After a
+    // carry r < h EPS < 2^59, so r + EPS cannot carry again.
+    __device__ __forceinline__ uint64_t fin() const
+    {
+        uint32_t c1, c2;
+        const uint32_t mid = __builtin_addc((uint32_t)(L >> 32), (uint32_t)H, 0u, &c1);
+        const uint32_t h = __builtin_addc((uint32_t)(H >> 32), 0u, c1, &c2);
+        const uint64_t lo = ((uint64_t)mid << 32) | (uint32_t)L;
+#if ZKGPU_RB_MADC
+        // gl_reduce128_rb's tail: the multiply-add's carry-out selects EPS
+        uint64_t r, cy;
+        uint32_t m;
+        asm("v_mad_u64_u32 %0, %1, %3, -1, %4\n\ts_nop 1\n\tv_cndmask_b32_e64 %2, 0, -1, %1"
+            : "=&v"(r), "=&s"(cy), "=&v"(m)
+            : "v"(h), "v"(lo));
+        return r + m;
+#else
+        return gl_reduce96(lo, h);
+#endif
+    }
+};
+
+// one three-round block; K: the block's seeds (ZKGPU_PSB3_K)
+__device__ __forceinline__ void psb3_block(uint64_t st[12], const uint32_t *K)
+{
+    st[0] = pow7(st[0]);
+    Dot2 d1(K[0], K[1]);
+#pragma unroll
+    for (int j = 0; j < 12; j++) d1.term(st[j], (uint32_t)ZKGPU_PSB3_P1.v[0][j]);
+    const uint64_t y1 = pow7(d1.fin());
+    Dot2 d2(K[2], K[3]);
+#pragma unroll
+    for (int j = 0; j < 12; j++) d2.term(st[j], (uint32_t)ZKGPU_PSB3_P2.v[0][j]);
+    d2.term(y1, (uint32_t)ZKGPU_PSB3_P1.v[0][0]);
+    const uint64_t y2 = pow7(d2.fin());
+    // output rows one at a time: one accumulator pair live
+    uint64_t out[12];
+#pragma unroll
+    for (int x = 0; x < 12; x++) {
+        Dot2 d(K[4 + 2 * x], K[5 + 2 * x]);
+#pragma unroll
+        for (int j = 0; j < 12; j++) d.term(st[j], (uint32_t)ZKGPU_PSB3_P3.v[x][j]);
+        d.term(y1, (uint32_t)ZKGPU_PSB3_P2.v[x][0]);
+        d.term(y2, (uint32_t)ZKGPU_PSB3_P1.v[x][0]);
+        out[x] = d.fin();
+    }
+#pragma unroll
+    for (int x = 0; x < 12; x++) st[x] = out[x];
+}
+
+// The 22 partial rounds as 7 three-round blocks and one textbook round; same
+// input / output contract as partial_rounds_blocks (in: PRE added, out: the
+// round-26 constants added), bit-identical after gl_canon.
+__device__ __forceinline__ void partial_rounds_pow3(uint64_t st[12])
+{
+#pragma unroll 1
+    for (int b = 0; b < ZKGPU_PSB3_NBLOCKS; b++) psb3_block(st, &ZKGPU_PSB3_K[b * ZKGPU_PSB3_BLOCK_WORDS]);
+    st[0] = pow7(st[0]);
+    if constexpr (ZKGPU_MDS_FFT)
+        mds_fft_fold(st, &ZKGPU_POSEIDON_RC[26 * 12]);
+    else
+        mds_fold(st, &ZKGPU_POSEIDON_RC[26 * 12]);
+}
+
+// ZKGPU_PSB_POW3 = 0 keeps the 11-round sparse blocks (A/B builds, tools/ab_lib.sh)
+#ifndef ZKGPU_PSB_POW3
+#define ZKGPU_PSB_POW3 1
+#endif
+__device__ __forceinline__ void partial_rounds(uint64_t st[12])
+{
+    if constexpr (ZKGPU_PSB_POW3)
+        partial_rounds_pow3(st);
+    else
+        partial_rounds_blocks(st);
+}
+
 __device__ __forceinline__ void perm_fast(uint64_t st[12])
 {
 #pragma unroll
     for (int s = 0; s < 12; s++) st[s] = gl_add(st[s], ZKGPU_POSEIDON_RC[s]);
     full_rounds_fold(st, 0, 4);
-    partial_rounds_blocks(st);
+    partial_rounds(st);
     full_rounds_fold(st, 26, 4);
 }
 
@@ -482,7 +631,7 @@ __device__ __forceinline__ void perm_fast4(uint64_t st[12])
         for (int s = 0; s < 12; s++) st[s] = gl_add(st[s], ZKGPU_POSEIDON_RC[s]);
         full_rounds_fold(st, 0, 4);
     }
-    partial_rounds_blocks(st);
+    partial_rounds(st);
     full_rounds_fold(st, 26, 3);
 #pragma unroll
     for (int s = 0; s < 12; s++) st[s] = pow7(st[s]);
@@ -496,7 +645,10 @@ __device__ __forceinline__ void perm_fast_tab(uint64_t st[12], const uint32_t *D
 #pragma unroll
     for (int s = 0; s < 12; s++) st[s] = gl_add(st[s], ZKGPU_POSEIDON_RC[s]);
     full_rounds_fold(st, 0, 4);
-    partial_rounds_blocks(st, D0, BL);
+    if constexpr (ZKGPU_PSB_POW3)
+        partial_rounds_pow3(st);  // its coefficients are instruction constants: no table
+    else
+        partial_rounds_blocks(st, D0, BL);
     full_rounds_fold(st, 26, 4);
 }
 

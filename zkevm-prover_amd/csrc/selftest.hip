@@ -61,6 +61,13 @@ __global__ void k_field_selftest_rb(uint64_t *out, const uint64_t *a, const uint
         r = d.fin();
         break;
     }
+    case 12: {  // the power blocks' two-accumulator reduction, L + 2^32 H (both < 2^58)
+        Dot2 d(0u, 0u);
+        d.L = x;
+        d.H = y;
+        r = d.fin();
+        break;
+    }
     default: break;
     }
     if (i < n) out[i] = gl_canon(r);
@@ -74,7 +81,7 @@ extern "C" int zkgpu_gl_field_selftest_rb_dev(uint64_t *out, const uint64_t *a, 
                                                uint64_t n, int op, int e)
 {
     if (!ctx().ready) return set_error(ZKGPU_ERR_INIT, "zkgpu_init() not called");
-    if (op < 0 || op > 11) return set_error(ZKGPU_ERR_ARG, "field_selftest_rb: unknown op %d", op);
+    if (op < 0 || op > 12) return set_error(ZKGPU_ERR_ARG, "field_selftest_rb: unknown op %d", op);
     if ((op == 6 || op == 7) && (e < 0 || e >= 192)) return set_error(ZKGPU_ERR_ARG, "field_selftest_rb: e %d", e);
     if ((op == 5 || op == 11) && !c) return set_error(ZKGPU_ERR_ARG, "field_selftest_rb: op %d needs c", op);
     if (!n) return 0;
