@@ -520,6 +520,34 @@ int zkgpu_qsplit_cols_dev(uint64_t *qq2, uint64_t ld2, const uint64_t *qq1, uint
 int zkgpu_h1h2_dev(uint64_t *h1, uint64_t h1_ld, uint64_t *h2, uint64_t h2_ld, const uint64_t *f, uint64_t f_ld,
                    const uint64_t *t, uint64_t t_ld, uint64_t n, uint32_t dim, uint64_t *missing_row);
 
+/* Multiset comparison of two n-row columns a and b of dimension dim (1, or 3 = three column-major
+ * components one leading dimension apart, as zkgpu_h1h2_dev): the distinct values whose
+ * multiplicity in a differs from their multiplicity in b.  A value is the canonical dim-tuple
+ * (v and v + p are the same value).  What a grand product that does not close is asked
+ * (host/starks.cpp z_all): for a permutation check num = f + gamma, den = t + gamma the answer is
+ * the offending values themselves.
+ * out (device, 2 * (1 + 3 * max_vals) words), two blocks of 1 + 3 * max_vals words:
+ *   block A  out[0] = the number of distinct values that occur in a with unequal counts, then
+ *            max_vals triples {the value's first row in a, its count in a, its count in b}
+ *            ordered by that row, ascending; UINT64_MAX, 0, 0 past the last
+ *   block B  the same for the values that occur in b: {first row in b, count in a, count in b}
+ * (a value on both sides with unequal counts is in both blocks).  Reported by value, not by row:
+ * a default value on millions of rows with one copy too many is ONE entry.
+ * The result does not depend on the launch geometry or on which thread claims a table slot:
+ * counts are atomic sums, first rows atomic minima, and the lists come from the reduction of
+ * zkgpu_nonzero_rows_dev over a flag on each value's first row.  Enqueued on the library stream,
+ * no host synchronisation; rows [n, ld) are not read; a == b is allowed.  ZKGPU_ERR_ARG, nothing
+ * queued: a_ld < n or b_ld < n, dim not 1 or 3, max_vals > 4096, n > 2^28, null pointers; n = 0
+ * writes two zero counts and padded lists.
+ * Scratch: the grow-only workspace the plookup shares, of
+ *   zkgpu_multiset_diff_workspace_bytes(n) = 16 m + 16 n + 8 ceil(ceil(n / 1024) / 2) + 16 * 4097
+ * bytes, m = the smallest power of two >= 4 n (0 for n = 0): a table of m slots x 4 u32 (the up
+ * to 2 n distinct values at load <= 0.5), two n-row flag columns, the reduction's block counts
+ * and the two row lists (host only, no GPU needed). */
+uint64_t zkgpu_multiset_diff_workspace_bytes(uint64_t n);
+int zkgpu_multiset_diff_dev(uint64_t *out, const uint64_t *a, uint64_t a_ld, const uint64_t *b, uint64_t b_ld,
+                            uint64_t n, uint32_t dim, uint32_t max_vals);
+
 /* 3 ext columns (ld >= n) -> interleaved n x 3 (the FRI polynomial layout, friProve.cpp) */
 int zkgpu_cols3_to_interleaved_dev(uint64_t *out, const uint64_t *cols, uint64_t ld, uint64_t n);
 

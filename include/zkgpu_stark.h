@@ -263,6 +263,39 @@ int zkgpu_stark_check_terms(void *handle, zxp_split_term *out, uint32_t max, uin
 int zkgpu_stark_check_named(void *handle, uint32_t slot, uint32_t *ids, uint64_t *values, uint32_t max,
                             uint32_t *n_failing);
 
+/* ---- a grand product that does not close: the values that keep it open
+ * calculateZ (starks.cpp:165-189) of a product whose total is not 1 fails the proof with
+ * "calculateZ: grand product <z> does not close".  Before that failure returns, the single-GPU
+ * prover compares the num and den tmpExp columns (dim 3) of the LOWEST such product as multisets
+ * (zkgpu_multiset_diff_dev, include/zkgpu.h, 16 values per side), reads the result back and
+ * keeps it; the message gains a tail naming, per side, how many distinct values are unmatched,
+ * the first one's row and its two counts.  The return code and the state the failed proof leaves
+ * are unchanged.
+ *   num[k] / den[k]  the k-th value, by its first row on that side, whose count in num differs
+ *                    from its count in den: {that row, count in num, count in den};
+ *                    {UINT64_MAX, 0, 0} past the last.  n_num / n_den count all of them.
+ * What the lists mean: for a permutation check (num = f + gamma, den = t + gamma) they are
+ * exactly the offending values and where they first occur -- a tuple on one side only, or a
+ * default value with one copy too many ("5000001 times against 5000000").  The per-row factors of
+ * a plookup or a connection product are not paired values: there the lists say only that the two
+ * columns differ.
+ * A proof whose products all close queues nothing of this: no kernel, no allocation, the same
+ * timers, the same proof; nothing is added to either memory plan's figure (the comparison's
+ * scratch is the library workspace, zkgpu_multiset_diff_workspace_bytes(n), taken on the failing
+ * path only).  When that scratch cannot be allocated the message says the comparison was skipped
+ * and ran stays 0.  The row-sharded prover keeps the plain message; zkgpu_stark_z_diag on its
+ * handle is refused (single-GPU provers only, as the constraint check). */
+#define ZKGPU_Z_DIAG_MAX 16
+typedef struct { uint64_t row, count_num, count_den; } zkgpu_z_diag_val;
+typedef struct {
+    uint32_t ran;       /* 1: the last prove failed at calculateZ and the comparison ran */
+    uint32_t z;         /* the lowest product that does not close (index into zctx) */
+    uint32_t n_open;    /* how many products do not close */
+    uint64_t n_num, n_den;                       /* distinct values with unequal counts, by side */
+    zkgpu_z_diag_val num[ZKGPU_Z_DIAG_MAX], den[ZKGPU_Z_DIAG_MAX];
+} zkgpu_z_diag;
+int zkgpu_stark_z_diag(void *handle, zkgpu_z_diag *out);
+
 /* ---- the Fiat-Shamir transcript the prover runs on the host, as the
  * reference's class Transcript (transcript.hpp:14-37, transcript.cpp:4-88):
  * Poseidon-GL sponge, 8-element rate, 4-element capacity.  Host code only

@@ -561,4 +561,212 @@ int h1h2_shard_place(uint64_t *h1, uint64_t h1_ld, uint64_t *h2, uint64_t h2_ld,
     return check_launch("h1h2 place");
 }
 
+// ---------------------------------------------------------------- multiset difference
+// The distinct values of two n-row columns a and b whose multiplicities
+// differ (the prover's calculateZ diagnosis: a permutation check that does not
+// close; include/zkgpu.h zkgpu_multiset_diff_dev).  One open-addressing table
+// of rows, keyed like the plookup's, holds the up to 2n distinct values of
+// both columns at load <= 0.5 (2^k >= 4n slots).  Row i of a has index i, row
+// i of b index n + i; per slot:
+//   slot    the SMALLEST index with the slot's key (atomicMin): below n it is
+//           the value's first row in a
+//   firstb  the value's first row in b (atomicMin)
+//   cnta / cntb  its rows in a / in b (atomicAdd)
+// Which thread claims an empty slot decides only WHERE a key lives, never
+// what the slot ends up holding: minima and sums do not depend on the order.
+// k_ms_flag then marks, for every slot with cnta != cntb, the value's first
+// row in a flag column per side, the nonzero-rows reduction (stark.hip,
+// independent of the launch geometry) lists the lowest max_vals of each, and
+// k_ms_emit looks every listed row's slot up again for its two counts.
+constexpr uint32_t MS_MAX_VALS = 4096;  // = NZ_MAX_ROWS (the lists come from k_nz_emit)
+
+static uint64_t ms_table_size(uint64_t n)
+{
+    if (!n) return 0;
+    uint64_t m = 1;
+    while (m < 4 * n) m <<= 1;
+    return m;
+}
+
+struct MsTable {
+    uint32_t *slot, *firstb, *cnta, *cntb;
+    uint64_t mask;
+    const uint64_t *a, *b;
+    uint64_t a_ld, b_ld, n;
+};
+
+// does the row with index g (a: g, b: n + g) hold key?
+template <int DIM>
+__device__ __forceinline__ bool ms_eq(const MsTable &T, uint32_t g, const uint64_t key[DIM])
+{
+    return g < T.n ? h12_eq<DIM>(T.a, T.a_ld, g, key) : h12_eq<DIM>(T.b, T.b_ld, g - (uint32_t)T.n, key);
+}
+
+template <int DIM>
+__global__ void __launch_bounds__(256) k_ms_insert(MsTable T)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = g < 2 * T.n;
+    const bool side = g >= T.n;
+    const uint64_t i = side ? g - T.n : g;
+    uint32_t *ctr = nullptr;
+    if (live) {
+        uint64_t key[DIM];
+        h12_key<DIM>(key, side ? T.b : T.a, side ? T.b_ld : T.a_ld, i);
+        uint64_t h = h12_hash<DIM>(key) & T.mask;
+        // bounded by the table size; 2n indices in >= 4n slots: a slot is always found
+        for (uint64_t probe = 0; probe <= T.mask; probe++, h = (h + 1) & T.mask) {
+            uint32_t cur = T.slot[h];
+            if (cur == H12_EMPTY) {
+                cur = atomicCAS(&T.slot[h], H12_EMPTY, (uint32_t)g);
+                if (cur == H12_EMPTY) cur = (uint32_t)g;
+            }
+            if (cur == (uint32_t)g || ms_eq<DIM>(T, cur, key)) {  // every index a slot ever holds has its key
+                if (cur > (uint32_t)g) atomicMin(&T.slot[h], (uint32_t)g);  // (a slot only ever decreases)
+                if (side && T.firstb[h] > (uint32_t)i) atomicMin(&T.firstb[h], (uint32_t)i);
+                ctr = side ? &T.cntb[h] : &T.cnta[h];
+                break;
+            }
+        }
+    }
+    // one add per wave for the lanes that share the first lane's counter (a
+    // permutation's default value sits on most rows), one per lane otherwise
+    const uint64_t todo = __ballot(ctr != nullptr);
+    if (!todo) return;
+    const int lead = __ffsll((unsigned long long)todo) - 1;
+    const uint64_t p = (uint64_t)ctr;
+    const uint64_t lp = ((uint64_t)(uint32_t)__shfl((int)(p >> 32), lead) << 32) | (uint32_t)__shfl((int)p, lead);
+    const uint64_t same = __ballot(ctr != nullptr && p == lp);
+    if (!ctr) return;
+    if (p != lp)
+        atomicAdd(ctr, 1u);
+    else if ((int)(threadIdx.x & 63) == lead)
+        atomicAdd(ctr, (uint32_t)__popcll(same));
+}
+
+// slot k with unequal counts -> flag the value's first row on each side it occurs on
+__global__ void __launch_bounds__(256) k_ms_flag(uint64_t *flaga, uint64_t *flagb, MsTable T)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > T.mask) return;
+    const uint32_t g = T.slot[k];
+    if (g == H12_EMPTY || T.cnta[k] == T.cntb[k]) return;
+    if (g < T.n) flaga[g] = 1;
+    const uint32_t fb = T.firstb[k];
+    if (fb != H12_EMPTY) flagb[fb] = 1;
+}
+
+// block y (0: a, 1: b) of out from the side's row list {count, rows ...}
+template <int DIM>
+__global__ void __launch_bounds__(256) k_ms_emit(uint64_t *out, const uint64_t *lista, const uint64_t *listb,
+                                                 uint32_t max_vals, MsTable T)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool side = blockIdx.y;
+    const uint64_t *list = side ? listb : lista;
+    uint64_t *o = out + (side ? 1 + 3ULL * max_vals : 0);
+    if (k == 0) o[0] = list[0];
+    if (k >= max_vals) return;
+    const uint64_t row = list[1 + k];
+    uint64_t ca = 0, cb = 0;
+    if (row < T.n) {
+        uint64_t key[DIM];
+        h12_key<DIM>(key, side ? T.b : T.a, side ? T.b_ld : T.a_ld, row);
+        uint64_t h = h12_hash<DIM>(key) & T.mask;
+        for (uint64_t probe = 0; probe <= T.mask; probe++, h = (h + 1) & T.mask) {
+            const uint32_t cur = T.slot[h];
+            if (cur == H12_EMPTY) break;
+            if (ms_eq<DIM>(T, cur, key)) {
+                ca = T.cnta[h];
+                cb = T.cntb[h];
+                break;
+            }
+        }
+    }
+    o[1 + 3ULL * k] = row;
+    o[2 + 3ULL * k] = ca;
+    o[3 + 3ULL * k] = cb;
+}
+
+// the layout of the workspace (include/zkgpu.h states the sum)
+struct MsLayout {
+    uint64_t m, table, flags, counts, lists, total;
+};
+static MsLayout ms_layout(uint64_t n)
+{
+    MsLayout L;
+    L.m = ms_table_size(n);
+    L.table = 0;                                                      // slot, firstb, cnta, cntb: 4 x m u32
+    L.flags = L.table + 16 * L.m;                                     // 2 flag columns of n u64
+    L.counts = L.flags + 16 * n;                                      // the nonzero-rows block counts
+    L.lists = L.counts + 8 * (((uint64_t)nonzero_rows_blocks(n) + 1) / 2);  // 2 lists of 1 + MS_MAX_VALS u64
+    L.total = L.lists + 2 * 8 * (1 + (uint64_t)MS_MAX_VALS);
+    return L;
+}
+
+uint64_t multiset_diff_workspace_bytes(uint64_t n) { return ms_layout(n).total; }
+
+int multiset_diff(uint64_t *out, const uint64_t *a, uint64_t a_ld, const uint64_t *b, uint64_t b_ld, uint64_t n,
+                  uint32_t dim, uint32_t max_vals, hipStream_t s)
+{
+    const MsLayout L = ms_layout(n);
+    char *w = (char *)workspace(4, L.total);
+    if (!w) return ZKGPU_ERR_OOM;
+    MsTable T;
+    T.slot = (uint32_t *)(w + L.table);
+    T.firstb = T.slot + L.m;
+    T.cnta = T.firstb + L.m;
+    T.cntb = T.cnta + L.m;
+    T.mask = L.m - 1;
+    T.a = a, T.b = b, T.a_ld = a_ld, T.b_ld = b_ld, T.n = n;
+    uint64_t *flaga = (uint64_t *)(w + L.flags), *flagb = flaga + n;
+    uint32_t *counts = (uint32_t *)(w + L.counts);
+    uint64_t *lista = (uint64_t *)(w + L.lists), *listb = lista + 1 + MS_MAX_VALS;
+    const uint32_t B = 256;
+    if (n) {
+        prof_begin(s);
+        // slot and firstb empty, the counts and the flags zero
+        if (check_hip(hipMemsetAsync(T.slot, 0xFF, 8 * L.m, s), "multiset_diff memset") ||
+            check_hip(hipMemsetAsync(T.cnta, 0, 8 * L.m + 16 * n, s), "multiset_diff memset"))
+            return ZKGPU_ERR_HIP;
+        if (dim == 1)
+            hipLaunchKernelGGL(k_ms_insert<1>, dim3(nblk2(2 * n, B)), dim3(B), 0, s, T);
+        else
+            hipLaunchKernelGGL(k_ms_insert<3>, dim3(nblk2(2 * n, B)), dim3(B), 0, s, T);
+        prof_end("k_multiset_insert", (double)dim * 8.0 * 2.0 * n, s);
+        prof_begin(s);
+        hipLaunchKernelGGL(k_ms_flag, dim3(nblk2(L.m, B)), dim3(B), 0, s, flaga, flagb, T);
+        prof_end("k_multiset_flag", 16.0 * (double)L.m, s);
+        if (check_launch("multiset_diff")) return ZKGPU_ERR_HIP;
+    }
+    int rc;
+    if ((rc = nonzero_rows(lista, counts, flaga, n, 1, n, max_vals, s)) ||
+        (rc = nonzero_rows(listb, counts, flagb, n, 1, n, max_vals, s)))
+        return rc;
+    prof_begin(s);
+    const dim3 grid(nblk2(max_vals ? max_vals : 1, B), 2);
+    if (dim == 1)
+        hipLaunchKernelGGL(k_ms_emit<1>, grid, dim3(B), 0, s, out, lista, listb, max_vals, T);
+    else
+        hipLaunchKernelGGL(k_ms_emit<3>, grid, dim3(B), 0, s, out, lista, listb, max_vals, T);
+    prof_end("k_multiset_emit", 2.0 * 8.0 * (1 + 3.0 * max_vals), s);
+    return check_launch("multiset_diff");
+}
+
 }  // namespace zk
+
+// the C-ABI of the multiset difference (include/zkgpu.h), beside its kernels
+extern "C" uint64_t zkgpu_multiset_diff_workspace_bytes(uint64_t n) { return zk::multiset_diff_workspace_bytes(n); }
+
+extern "C" int zkgpu_multiset_diff_dev(uint64_t *out, const uint64_t *a, uint64_t a_ld, const uint64_t *b,
+                                       uint64_t b_ld, uint64_t n, uint32_t dim, uint32_t max_vals)
+{
+    if (!zk::ctx().ready) return zk::set_error(ZKGPU_ERR_INIT, "zkgpu_init() not called");
+    if (!out || (n && (!a || !b))) return zk::set_error(ZKGPU_ERR_ARG, "multiset_diff: null pointer");
+    if (dim != 1 && dim != 3) return zk::set_error(ZKGPU_ERR_ARG, "multiset_diff: dim must be 1 or 3");
+    if (max_vals > zk::MS_MAX_VALS)
+        return zk::set_error(ZKGPU_ERR_ARG, "multiset_diff: max_vals %u > %u", max_vals, zk::MS_MAX_VALS);
+    if (n > (1ULL << 28)) return zk::set_error(ZKGPU_ERR_ARG, "multiset_diff: more than 2^28 rows");
+    if (a_ld < n || b_ld < n) return zk::set_error(ZKGPU_ERR_ARG, "multiset_diff: ld < n");
+    return zk::multiset_diff(out, a, a_ld, b, b_ld, n, dim, max_vals, zk::ctx().stream);
+}

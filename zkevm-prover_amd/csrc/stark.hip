@@ -833,8 +833,10 @@ static int gather_rows(uint64_t *out, const uint64_t *src, uint64_t ld, uint32_t
     return check_launch("k_gather_rows");
 }
 
-// counts: nblk(n, NZ_BLOCK) words of device scratch
-static int nonzero_rows(uint64_t *out, uint32_t *counts, const uint64_t *cols, uint64_t ld, uint32_t ncols, uint64_t n,
+// counts: nonzero_rows_blocks(n) words of device scratch
+uint32_t nonzero_rows_blocks(uint64_t n) { return nblk(n, NZ_BLOCK); }
+
+int nonzero_rows(uint64_t *out, uint32_t *counts, const uint64_t *cols, uint64_t ld, uint32_t ncols, uint64_t n,
                         uint32_t max_rows, hipStream_t s)
 {
     const uint32_t nblocks = nblk(n, NZ_BLOCK);

@@ -112,6 +112,11 @@ int copy_rows(uint64_t *dst, uint64_t dld, uint64_t drow0, const uint32_t *dcols
 int zxp_eval(const ZxpLaunch &L, hipStream_t s);
 // the same at the rows rows[0 .. n_rows) (device), stores compact (k_zxp_eval_rows)
 int zxp_eval_rows(const ZxpLaunch &L, const uint64_t *rows, uint32_t n_rows, hipStream_t s);
+// the nonzero rows of a column-major section (k_nz_count / k_nz_emit): out = 1 + max_rows words,
+// counts = nonzero_rows_blocks(n) words of device scratch
+uint32_t nonzero_rows_blocks(uint64_t n);
+int nonzero_rows(uint64_t *out, uint32_t *counts, const uint64_t *cols, uint64_t ld, uint32_t ncols, uint64_t n,
+                 uint32_t max_rows, hipStream_t s);
 size_t calculate_z_scratch_words(uint64_t n);
 int calculate_z(uint64_t *z, uint64_t z_ld, const uint64_t *num, uint64_t num_ld, const uint64_t *den,
                 uint64_t den_ld, uint64_t n, const uint64_t z0[3], uint64_t *scratch, uint64_t *total_dev, hipStream_t s);
@@ -135,6 +140,10 @@ int qsplit(uint64_t *qq2, uint64_t ld2, const uint64_t *qq1, uint64_t ld1, uint6
 int cols3_to_interleaved(uint64_t *out, const uint64_t *cols, uint64_t ld, uint64_t n, hipStream_t s);
 int h1h2(uint64_t *h1, uint64_t h1_ld, uint64_t *h2, uint64_t h2_ld, const uint64_t *f, uint64_t f_ld,
          const uint64_t *t, uint64_t t_ld, uint64_t n, uint32_t dim, uint64_t *missing_row, hipStream_t s);
+// the distinct values of two columns whose multiplicities differ (h1h2.hip "multiset difference")
+uint64_t multiset_diff_workspace_bytes(uint64_t n);
+int multiset_diff(uint64_t *out, const uint64_t *a, uint64_t a_ld, const uint64_t *b, uint64_t b_ld, uint64_t n,
+                  uint32_t dim, uint32_t max_vals, hipStream_t s);
 int merkle_open_strided(uint64_t *vals, uint64_t *sibs, const uint64_t *nodes, const uint64_t *src, uint64_t ncols,
                         uint64_t nrows, uint64_t row_stride, uint64_t col_stride, const uint64_t *idx, uint64_t nq,
                         hipStream_t s);

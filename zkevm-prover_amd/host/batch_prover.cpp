@@ -270,8 +270,15 @@ static int prove(const std::string &config_path, const Shard &sh)
     const uint64_t len = zkgpu_stark_proof_len(h);
     if (len != flat_len(info)) throw std::runtime_error("proof length mismatch");
     std::vector<uint64_t> flat(len);
-    if (sh.stream_trace ? zkgpu_stark_prove_from_rows(h, cm1.data(), 1, flat.data()) : zkgpu_stark_prove(h, flat.data()))
-        throw std::runtime_error(std::string("prove: ") + zkgpu_stark_last_error());
+    if (sh.stream_trace ? zkgpu_stark_prove_from_rows(h, cm1.data(), 1, flat.data()) : zkgpu_stark_prove(h, flat.data())) {
+        // a grand product that does not close (no proof file is written): the diagnosis is in the
+        // message; which context of the starkinfo the product is, from the order of the triples
+        std::string msg = std::string("prove: ") + zkgpu_stark_last_error();
+        zkgpu_z_diag zd;
+        if (sh.comm.empty() && !zkgpu_stark_z_diag(h, &zd) && zd.n_open)
+            msg += "; grand product " + std::to_string(zd.z) + " is " + si.z_context(zd.z);
+        throw std::runtime_error(msg);
+    }
     const auto t2 = clk::now();
     if (sh.rank == 0) write_outputs(key("outputPath"), flat.data(), len, info, publics);
     const auto t3 = clk::now();

@@ -734,6 +734,10 @@ public:
         return fail("stark (sharded): check_set is single-GPU only (the n-domain sections live in row blocks on the "
                     "ranks)");
     }
+    int z_diag(zkgpu_z_diag *) const override
+    {
+        return fail("stark (sharded): z_diag: single-GPU provers only (a rank holds a row block of num and den)");
+    }
     int check_names_set(int) override
     {
         return fail("stark (sharded): check_names_set is single-GPU only (as check_set)");

@@ -156,6 +156,22 @@ void StarkInfo::load(const json::Value &j)
     for (const auto &kv : e2p.o) exp2pol[kv.first] = kv.second.u64();
 }
 
+std::string StarkInfo::z_context(uint64_t z) const
+{
+    const struct {
+        const char *what, *key;
+        size_t n;
+    } kinds[3] = {{"plookup", "puCtx", puCtx.size()},
+                  {"permutation check", "peCtx", peCtx.size()},
+                  {"connection check", "ciCtx", ciCtx.size()}};
+    for (const auto &k : kinds) {
+        if (z < k.n)
+            return std::string(k.what) + " " + std::to_string(z) + " (" + k.key + "[" + std::to_string(z) + "])";
+        z -= k.n;
+    }
+    return "no context of the starkinfo";
+}
+
 StarkInfo StarkInfo::from_file(const std::string &path)
 {
     std::ifstream f(path);

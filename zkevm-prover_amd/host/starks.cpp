@@ -1457,6 +1457,7 @@ public:
         probe_valid = false;
         check_pending = false;
         check_res = zkgpu_check_result{};
+        zdiag = zkgpu_z_diag{};
         names_ran = false;
         for (auto &v : names_ids) v.clear();
         for (auto &v : names_vals) v.clear();
@@ -1608,8 +1609,68 @@ public:
                       S.sec[SEC_TMP_N] + (uint64_t)zctx[3 * z + 1] * N, N};
         std::vector<int> closes(info.n_zctx + 1, 0);
         CK(zkgpu_calculate_z_many_dev(req.data(), info.n_zctx, N, closes.data()));
-        for (uint32_t z = 0; z < info.n_zctx; z++)
-            if (!closes[z]) return fail("calculateZ: grand product %u does not close", z);
+        uint32_t n_open = 0, first = 0;
+        for (uint32_t z = info.n_zctx; z-- > 0;)
+            if (!closes[z]) n_open++, first = z;
+        return n_open ? z_open(first, n_open) : 0;
+    }
+
+    // ---- a grand product that does not close: which values keep it open
+    // The failing path of z_all (a proof whose products close queues nothing
+    // of this): the multiset comparison (zkgpu_multiset_diff_dev) of the num
+    // and den tmpExp columns of the lowest open product, read back into
+    // zdiag before the failure returns.  For a permutation check (num = f +
+    // gamma, den = t + gamma) the lists are the offending values and where
+    // they first occur; the per-row factors of a plookup or connection
+    // product are not paired values, there the lists say only that the
+    // columns differ.  The 98-word result block lives for this call only.
+    zkgpu_z_diag zdiag = {};
+
+    int z_open(uint32_t z, uint32_t n_open)
+    {
+        zdiag = zkgpu_z_diag{};
+        zdiag.z = z;
+        zdiag.n_open = n_open;
+        constexpr uint32_t M = ZKGPU_Z_DIAG_MAX, BLK = 1 + 3 * M;
+        uint64_t h[2 * BLK];
+        void *dev = nullptr;
+        int rc = zkgpu_dev_malloc(&dev, sizeof h);
+        if (!rc)
+            rc = zkgpu_multiset_diff_dev((uint64_t *)dev, S.sec[SEC_TMP_N] + (uint64_t)zctx[3 * z] * N, N,
+                                         S.sec[SEC_TMP_N] + (uint64_t)zctx[3 * z + 1] * N, N, N, 3, M);
+        if (!rc) rc = zkgpu_memcpy_d2h(h, dev, sizeof h);
+        const std::string why = rc ? zkgpu_last_error() : "";
+        (void)zkgpu_dev_free(dev);
+        if (rc)
+            return fail("calculateZ: grand product %u does not close (%u of %u do not); the comparison of its num and "
+                        "den columns was skipped: %s", z, n_open, info.n_zctx, why.c_str());
+        zdiag.ran = 1;
+        zdiag.n_num = h[0];
+        zdiag.n_den = h[BLK];
+        for (uint32_t k = 0; k < M; k++) {
+            zdiag.num[k] = {h[1 + 3 * k], h[2 + 3 * k], h[3 + 3 * k]};
+            zdiag.den[k] = {h[BLK + 1 + 3 * k], h[BLK + 2 + 3 * k], h[BLK + 3 + 3 * k]};
+        }
+        char side[2][160];
+        for (int b = 0; b < 2; b++) {
+            const uint64_t cnt = b ? zdiag.n_den : zdiag.n_num;
+            const zkgpu_z_diag_val &v = b ? zdiag.den[0] : zdiag.num[0];
+            const char *name = b ? "den" : "num";
+            if (cnt)
+                snprintf(side[b], sizeof side[b], "%llu value(s) of %s unmatched, the first at row %llu (%llu in num, "
+                         "%llu in den)", (unsigned long long)cnt, name, (unsigned long long)v.row,
+                         (unsigned long long)v.count_num, (unsigned long long)v.count_den);
+            else
+                snprintf(side[b], sizeof side[b], "no value of %s unmatched", name);
+        }
+        return fail("calculateZ: grand product %u does not close (%u of %u do not): %s; %s", z, n_open, info.n_zctx,
+                    side[0], side[1]);
+    }
+
+    virtual int z_diag(zkgpu_z_diag *out) const
+    {
+        if (!out) return fail("z_diag: null buffer");
+        *out = zdiag;
         return 0;
     }
 
@@ -1910,6 +1971,7 @@ int zkgpu_stark_probe_set(void *h, const uint64_t *rows_n, uint32_t n_rows_n, co
 }
 int zkgpu_stark_check_set(void *h, uint32_t mode) { return ((Starks *)h)->check_set(mode); }
 int zkgpu_stark_check_result(void *h, zkgpu_check_result *out) { return ((Starks *)h)->check_result(out); }
+int zkgpu_stark_z_diag(void *h, zkgpu_z_diag *out) { return ((Starks *)h)->z_diag(out); }
 int zkgpu_stark_check_names_set(void *h, int on) { return ((Starks *)h)->check_names_set(on); }
 int zkgpu_stark_check_terms(void *h, zxp_split_term *out, uint32_t max, uint32_t *n)
 {

@@ -101,6 +101,9 @@ struct StarkInfo {
 
     void load(const json::Value &j);  // stark_info.cpp:21-454
     static StarkInfo from_file(const std::string &path);
+    // which context grand product z of the prover is: ProverInfo builds the (num, den, Z) triples
+    // in the order puCtx, peCtx, ciCtx -> "permutation check 0 (peCtx[0])"
+    std::string z_context(uint64_t z) const;
 };
 
 // The GPU prover's instance description derived from a StarkInfo; owns every

@@ -115,6 +115,8 @@ _SIGS = {
     "zkgpu_scale_by_powers_dev": (ctypes.c_int, [vp, u64, u32, u64, u64]),
     "zkgpu_cols3_to_interleaved_dev": (ctypes.c_int, [vp, vp, u64, u64]),
     "zkgpu_h1h2_dev": (ctypes.c_int, [vp, u64, vp, u64, vp, u64, vp, u64, u64, u32, pu64]),
+    "zkgpu_multiset_diff_workspace_bytes": (u64, [u64]),
+    "zkgpu_multiset_diff_dev": (ctypes.c_int, [vp, vp, u64, vp, u64, u64, u32, u32]),
     "zkgpu_h1h2_shard_route": (ctypes.c_int, [vp, u64, vp, vp, vp, u64, vp, u64, u64, u64, u32, u32]),
     "zkgpu_h1h2_shard_owner": (ctypes.c_int, [vp, vp, u64, u32, pu64]),
     "zkgpu_h1h2_shard_counts": (ctypes.c_int, [vp, vp, pu64, vp, vp, u64, u64, u64]),
@@ -848,6 +850,21 @@ def h1h2_dev(h1, h1_ld, h2, h2_ld, f, f_ld, t, t_ld, n, dim):
         return miss.value
     _check(rc, "zkgpu_h1h2_dev")
     return None
+
+
+def multiset_diff_workspace_bytes(n):
+    """device scratch bytes of multiset_diff_dev at n rows (no GPU needed)"""
+    return int(lib().zkgpu_multiset_diff_workspace_bytes(n))
+
+
+def multiset_diff_dev(out, a, a_ld, b, b_ld, n, dim, max_vals):
+    """out (device, 2 * (1 + 3 * max_vals) words): per side, the number of
+    distinct values of the n-row columns a / b (dim 1 or 3, column-major)
+    whose counts in a and in b differ, then max_vals triples {first row on
+    that side, count in a, count in b} by ascending row, (2^64 - 1, 0, 0)
+    past the last (zkgpu_multiset_diff_dev; queued on the library stream)"""
+    _check(lib().zkgpu_multiset_diff_dev(_addr(out), _addr(a), a_ld, _addr(b), b_ld, n, dim, max_vals),
+           "zkgpu_multiset_diff_dev")
 
 
 # calculateH1H2 over row-sharded f / t (include/zkgpu.h zkgpu_h1h2_shard_*;

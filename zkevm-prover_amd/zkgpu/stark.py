@@ -65,6 +65,21 @@ class CheckResult(ctypes.Structure):
                 ("value", ctypes.c_uint64 * 3), ("alpha", ctypes.c_uint64 * 3)]
 
 
+Z_DIAG_MAX = 16
+
+
+class ZDiagVal(ctypes.Structure):
+    """zkgpu_z_diag_val (include/zkgpu_stark.h)"""
+    _fields_ = [("row", ctypes.c_uint64), ("count_num", ctypes.c_uint64), ("count_den", ctypes.c_uint64)]
+
+
+class ZDiag(ctypes.Structure):
+    """zkgpu_z_diag (include/zkgpu_stark.h)"""
+    _fields_ = [("ran", ctypes.c_uint32), ("z", ctypes.c_uint32), ("n_open", ctypes.c_uint32),
+                ("n_num", ctypes.c_uint64), ("n_den", ctypes.c_uint64), ("num", ZDiagVal * Z_DIAG_MAX),
+                ("den", ZDiagVal * Z_DIAG_MAX)]
+
+
 _slib = None
 
 
@@ -97,6 +112,7 @@ def slib():
             ("zkgpu_stark_probe_read", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp, u64]),
             ("zkgpu_stark_check_set", ctypes.c_int, [vp, ctypes.c_uint32]),
             ("zkgpu_stark_check_result", ctypes.c_int, [vp, ctypes.POINTER(CheckResult)]),
+            ("zkgpu_stark_z_diag", ctypes.c_int, [vp, ctypes.POINTER(ZDiag)]),
             ("zkgpu_stark_check_names_set", ctypes.c_int, [vp, ctypes.c_int]),
             ("zkgpu_stark_check_terms", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp]),
             ("zkgpu_stark_check_named", ctypes.c_int, [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp]),
@@ -464,6 +480,22 @@ class GpuStark:
         rows = [int(x) for x in r.rows if x != 2**64 - 1]
         return {"ran": int(r.ran), "n_bad": int(r.n_bad), "rows": rows, "value": [int(x) for x in r.value],
                 "alpha": [int(x) for x in r.alpha]}
+
+    def z_diag(self):
+        """why the last proof failed at calculateZ (zkgpu_stark_z_diag):
+        dict(ran, z (the lowest grand product that does not close, index into
+        z_ctx), n_open, n_num, n_den, num, den); num / den list up to
+        Z_DIAG_MAX (first row on that side, count in num, count in den) of
+        the distinct values whose counts in the product's num and den columns
+        differ, by ascending row.  ran = 0: no such failure, or the
+        comparison was skipped."""
+        r = ZDiag()
+        _check(slib().zkgpu_stark_z_diag(self.h, ctypes.byref(r)), "zkgpu_stark_z_diag")
+        def vals(a):
+            return [(int(v.row), int(v.count_num), int(v.count_den)) for v in a if v.row != 2**64 - 1]
+
+        return {"ran": int(r.ran), "z": int(r.z), "n_open": int(r.n_open), "n_num": int(r.n_num),
+                "n_den": int(r.n_den), "num": vals(r.num), "den": vals(r.den)}
 
     def check_names_set(self, on=True):
         """naming of every later checked proof (zkgpu_stark_check_names_set):

@@ -16,7 +16,8 @@ reference tree, so the tests write them for a zkgpu.synthetic.SyntheticStark:
   zkin_text(...)       the zkin JSON the driver must write, as text
 
 Committed polynomial order (cm_n / cm_2ns): the cm1 columns, then h1 / h2 of
-each plookup, then the Z of each plookup and of each permutation context --
+each plookup, then the Z of each plookup and of each permutation context (the
+instance's permutation checks first, peCtx[0 ..), then its h products) --
 the positions transposeH1H2Columns / transposeZColumns read (starks.cpp:14,
 406-520) -- then the other stage-2/3 columns and the quotient pieces.
 """
@@ -82,6 +83,9 @@ def _committed_order(b, inst):
         b.committed("cm2_n", lk["h2"], lk["dim"])
     for lk in inst.lookups:
         b.committed("cm3_n", lk["z"], 3)
+    # the Z columns in peCtx order: the permutation checks, then the m products of the h columns
+    for pe in inst.perms:
+        b.committed("cm3_n", pe["z"], 3)
     for j in range(inst.m):
         b.committed("cm3_n", inst.z_ctx[j][2], 3)
     for j in range(inst.m):
@@ -145,8 +149,10 @@ def starkinfo(inst):
     # contexts (stark_info.cpp:149-186): expressions by id, exp2pol maps them to tmpExp_n
     pu = [{"tExpId": b.exp(lk["t"], lk["dim"]), "fExpId": b.exp(lk["f"], lk["dim"]), "h1Id": 0, "h2Id": 0, "zId": 0,
            "c1Id": 0, "numId": b.exp(lk["num"], 3), "denId": b.exp(lk["den"], 3), "c2Id": 0} for lk in inst.lookups]
-    pe = [{"tExpId": 0, "fExpId": 0, "zId": 0, "c1Id": 0, "numId": b.exp(inst.z_ctx[j][0], 3),
-           "denId": b.exp(inst.z_ctx[j][1], 3), "c2Id": 0} for j in range(inst.m)]
+    pe = [{"tExpId": b.exp(q["t"], 3), "fExpId": b.exp(q["f"], 3), "zId": 0, "c1Id": 0, "numId": b.exp(q["num"], 3),
+           "denId": b.exp(q["den"], 3), "c2Id": 0} for q in inst.perms]
+    pe += [{"tExpId": 0, "fExpId": 0, "zId": 0, "c1Id": 0, "numId": b.exp(inst.z_ctx[j][0], 3),
+            "denId": b.exp(inst.z_ctx[j][1], 3), "c2Id": 0} for j in range(inst.m)]
     qs = [b.pol("cm4_2ns", 3 * p, 3) for p in range(inst.q_deg)]
     ev = []
     for sec, col, dim, prime in inst.evmap:

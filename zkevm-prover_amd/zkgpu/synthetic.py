@@ -13,6 +13,9 @@ Starks::genProof (starks.cpp:9-404):
              #1 dim 1: C in T2, T2 = T0 with row 0 replaced by T0[N/2] (a
                 duplicate value, so the "last table row" rule matters)
              A, B, C are cm1 columns filled from the tables at shifted rows
+  permutations n_perms permutation checks (0 by default) between two pairs of cm1
+             columns: (A, B) pseudo-random, (C, D) = (A, B) rotated by PERM_ROT
+             rows (step1), so the two pairs hold the same multiset of tuples
   stage 2    challenges u = ch[0], defVal = ch[1];
              m extension columns h_j = sum_k a[s_j+k] u^(k+1) + defVal (cm2, 3m cols);
              plookup f/t into tmpExp, then h1/h2 = calculateH1H2(f, t) (cm2)
@@ -21,7 +24,11 @@ Starks::genProof (starks.cpp:9-404):
              Z_j = grand product of num_j/den_j (calculateZ, polinomial.hpp:586-607);
              it closes because den is num shifted by one row (cm3, 3m cols);
              plookup Z: num = (1+beta)(gamma+f)(gamma(1+beta) + t + beta t'),
-             den = (gamma(1+beta) + h1 + beta h2)(gamma(1+beta) + h2 + beta h1')
+             den = (gamma(1+beta) + h1 + beta h2)(gamma(1+beta) + h2 + beta h1');
+             permutation: f = A + u B, t = C + u D (stage 2, tmpExp, dim 3),
+             num = f + gamma, den = t + gamma (step3prev), Z their grand
+             product: it closes exactly when the tuples of (A, B) and (C, D)
+             are the same multiset
   stage 4    alpha = ch[4]; C = Horner_alpha of all constraints; q = C / Z_H
              (step42ns semantics, op 69), split into qDeg = 2 pieces (cm4, 6 cols)
   stage 5    xi = ch[7]; evals (evmap); v1 = ch[5], v2 = ch[6];
@@ -111,7 +118,8 @@ class Program:
 
 class SyntheticStark:
     def __init__(self, n_bits=10, blowup_bits=1, t=4, m=2, n_k=3, n_queries=16, fri_steps=None, n_publics=8,
-                 seed=0x5EED, n_free=0, n_lookups=2, q_deg=2, with_step3=True, n_free2=0, n_free3=0, n_free_tmp=0):
+                 seed=0x5EED, n_free=0, n_lookups=2, q_deg=2, with_step3=True, n_free2=0, n_free3=0, n_free_tmp=0,
+                 n_perms=0):
         self.n_bits = n_bits
         self.n_bits_ext = n_bits + blowup_bits
         self.blowup_bits = blowup_bits
@@ -127,6 +135,10 @@ class SyntheticStark:
         base = 3 * t + n_free
         self.cm1_lk = list(range(base, base + len(self.c_t)))
         self.n_cm1 = base + len(self.c_t)
+        # permutation checks: cm1 columns A, B (random), C, D (their rotation), after the lookup columns
+        self.n_perms = n_perms
+        self.perms = [{"cols": list(range(self.n_cm1 + 4 * k, self.n_cm1 + 4 * k + 4))} for k in range(n_perms)]
+        self.n_cm1 += 4 * n_perms
         # plookup contexts: dim, f/t tmp cols, h1/h2 cm2 cols, num/den tmp cols, Z cm3 col
         self.lookups = []
         cm2, tmp, cm3 = 3 * m, 6 * m, 3 * m
@@ -137,6 +149,11 @@ class SyntheticStark:
             self.lookups.append(lk)
             cm2 += 2 * d
             tmp += 2 * d + 6
+            cm3 += 3
+        # permutation contexts: f / t / num / den tmp cols (dim 3 each), Z cm3 col
+        for pe in self.perms:
+            pe.update({"f": tmp, "t": tmp + 3, "num": tmp + 6, "den": tmp + 9, "z": cm3})
+            tmp += 12
             cm3 += 3
         self.cm2_free = list(range(cm2, cm2 + n_free2))
         self.n_cm2 = cm2 + n_free2
@@ -170,6 +187,7 @@ class SyntheticStark:
         assert all(self.groups), "too many stage-2 groups for the cm1 width"
         self.z_ctx = [(6 * j, 6 * j + 3, 3 * j) for j in range(m)]  # (num tmp col, den tmp col, z cm3 col)
         self.z_ctx += [(lk["num"], lk["den"], lk["z"]) for lk in self.lookups]
+        self.z_ctx += [(pe["num"], pe["den"], pe["z"]) for pe in self.perms]
         self.pu = [(lk["f"], lk["t"], lk["h1"], lk["h2"], lk["dim"]) for lk in self.lookups]
         self._build_evmap()
         self.programs = {
@@ -206,6 +224,9 @@ class SyntheticStark:
         for lk in self.lookups:
             ev.append((SEC_CM3_2NS, lk["z"], 3, 0))
             ev.append((SEC_CM3_2NS, lk["z"], 3, 1))
+        for pe in self.perms:
+            ev.append((SEC_CM3_2NS, pe["z"], 3, 0))
+            ev.append((SEC_CM3_2NS, pe["z"], 3, 1))
         if self.with_step3:
             ev.append((SEC_CM3_2NS, self.cm3_w, 3, 0))
         for j, c in enumerate(self.cm2_free):
@@ -235,6 +256,8 @@ class SyntheticStark:
 
     # rows of the tables the lookup columns read: A, B at T[i+5] (row 0: T[11]), C at T2[i+7]
     LK_SHIFT, LK_SHIFT0, LK_SHIFT_C = 5, 11, 7
+    # (C, D)[i] = (A, B)[i + PERM_ROT] of every permutation check
+    PERM_ROT = 9
 
     def _prog_step1(self):
         """Trace derivation (executor stand-in): a[3j+2] = a[3j] a[3j+1] K_j + a[3j];
@@ -257,7 +280,23 @@ class SyntheticStark:
             p.op(COPY, p.col(SEC_CM1_N, c), t)
         if len(self.cm1_lk) > 2:
             p.op(COPY, p.col(SEC_CM1_N, self.cm1_lk[2]), p.col(SEC_CONST_N, self.c_t[2], self.LK_SHIFT_C))
+        for pe in self.perms:
+            a, b, c, d = pe["cols"]
+            p.op(COPY, p.col(SEC_CM1_N, c), p.col(SEC_CM1_N, a, self.PERM_ROT))
+            p.op(COPY, p.col(SEC_CM1_N, d), p.col(SEC_CM1_N, b, self.PERM_ROT))
         return p
+
+    def _pe_ft(self, p, pe, cm1_sec):
+        """(f, t) temps of a permutation check: f = A + u B, t = C + u D."""
+        u = p.chal(0)
+        a, b, c, d = pe["cols"]
+        f = p.tmp3()
+        p.op(MUL, f, u, p.col(cm1_sec, b))
+        p.op(ADD, f, f, p.col(cm1_sec, a))
+        t = p.tmp3()
+        p.op(MUL, t, u, p.col(cm1_sec, d))
+        p.op(ADD, t, t, p.col(cm1_sec, c))
+        return f, t
 
     def _lk_ft(self, p, k, cm1_sec, const_sec, shift_t):
         """(f, t') operands/temps of plookup k: f = A + u B | C, t = T0 + u T1 | T2 (row shift shift_t)."""
@@ -323,6 +362,10 @@ class SyntheticStark:
             f, t = self._lk_ft(p, k, SEC_CM1_N, SEC_CONST_N, 0)
             p.op(COPY, self._lk_col(p, SEC_TMP_N, lk["f"], lk["dim"]), f)
             p.op(COPY, self._lk_col(p, SEC_TMP_N, lk["t"], lk["dim"]), t)
+        for pe in self.perms:
+            f, t = self._pe_ft(p, pe, SEC_CM1_N)
+            p.op(COPY, p.col3(SEC_TMP_N, pe["f"]), f)
+            p.op(COPY, p.col3(SEC_TMP_N, pe["t"]), t)
         # cm2 fillers: a * b' + K
         if self.cm2_free:
             r = p.tmp1()
@@ -351,6 +394,9 @@ class SyntheticStark:
             h1n = self._lk_col(p, SEC_CM2_N, lk["h1"], d, 1)
             self._emit_lk_num_den(p, lk, f, tt, tn, h1, h2, h1n, p.col3(SEC_TMP_N, lk["num"]),
                                   p.col3(SEC_TMP_N, lk["den"]))
+        for pe in self.perms:
+            p.op(ADD, p.col3(SEC_TMP_N, pe["num"]), p.col3(SEC_TMP_N, pe["f"]), gamma)
+            p.op(ADD, p.col3(SEC_TMP_N, pe["den"]), p.col3(SEC_TMP_N, pe["t"]), gamma)
         # tmpExp fillers: (cm2 filler)' + a
         for j, c in enumerate(self.tmp_free):
             src = (p.col(SEC_CM2_N, self.cm2_free[j % len(self.cm2_free)], 1) if self.cm2_free
@@ -449,6 +495,24 @@ class SyntheticStark:
                 return r
             out.append(c_lk_first)
             out.append(c_lk_z)
+        for pe in self.perms:
+            def c_pe_first(pe=pe):
+                r = p.tmp3()
+                p.op(SUB, r, p.col3(SEC_CM3_2NS, pe["z"]), p.lit(1))
+                p.op(MUL, r, r, p.col(SEC_CONST_2NS, self.l_first))
+                return r
+
+            def c_pe_z(pe=pe):
+                gamma = p.chal(2)
+                f, t = self._pe_ft(p, pe, SEC_CM1_2NS)
+                p.op(ADD, f, f, gamma)
+                p.op(ADD, t, t, gamma)
+                p.op(MUL, t, t, p.col3(SEC_CM3_2NS, pe["z"], nxt))
+                p.op(MUL, f, f, p.col3(SEC_CM3_2NS, pe["z"]))
+                p.op(SUB, t, t, f)
+                return t
+            out.append(c_pe_first)
+            out.append(c_pe_z)
         return out
 
     def _prog_step42ns(self):
@@ -476,6 +540,7 @@ class SyntheticStark:
             cols += [(SEC_CM2_2NS, lk["h1"], lk["dim"]), (SEC_CM2_2NS, lk["h2"], lk["dim"])]
         cols += [(SEC_CM3_2NS, 3 * j, 3) for j in range(self.m)]
         cols += [(SEC_CM3_2NS, lk["z"], 3) for lk in self.lookups]
+        cols += [(SEC_CM3_2NS, pe["z"], 3) for pe in self.perms]
         if self.with_step3:
             cols += [(SEC_CM3_2NS, self.cm3_w, 3)]
         cols += [(SEC_CM2_2NS, c, 1) for c in self.cm2_free]
@@ -541,7 +606,8 @@ class SyntheticStark:
         return inst
 
     def random_cm1_cols(self):
-        return [c for c in range(3 * self.t + self.n_free) if c >= 3 * self.t or c % 3 != 2]
+        return ([c for c in range(3 * self.t + self.n_free) if c >= 3 * self.t or c % 3 != 2] +
+                [c for pe in self.perms for c in pe["cols"][:2]])
 
     def random_const_cols(self):
         """K_k and the random tables T0, T1 (T2 is derived by step0)."""
