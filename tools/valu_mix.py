@@ -30,7 +30,8 @@ LABELS = [
     (r"^zk::k_leaves_cols\b", "k_leaves_cols"),
     (r"^zk::k_merkle_level\(", "k_merkle_level"),
     (r"^zk::k_merkle_level_lp\b", "k_merkle_level_lp"),
-    (r"^void zk::k_ntt_pass<(\d+), (\d+), (true|false), (true|false)>", None),
+    # every role / input / post-scale instantiation of a radix and direction under one label
+    (r"^void zk::k_ntt_pass<(\d+), (\d+), (true|false), (true|false)[^>]*>", None),
 ]
 
 

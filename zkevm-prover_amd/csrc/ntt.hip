@@ -14,8 +14,11 @@
 //   workgroup moves 16 independent sub-DFTs (16 consecutive j' = 128-byte
 //   runs per row, so every global access is a full 128 B line), does the
 //   radix-2 DIF butterflies in LDS and applies the twiddles on the way out.
-//   Zero padding (LDE) is a predicated load in the first NTT pass; the
-//   1/n * shift^k factor of the LDE is fused into the last INTT pass.
+//   Zero padding (LDE) costs the first NTT pass nothing (n -> 2n: the zero
+//   half is not loaded) or a compare per load; the 1/n * shift^k factor of
+//   the LDE is fused into the last INTT pass.  What a launch is (first /
+//   middle / last pass, table or recurrence twiddles, padding, post-scale) is
+//   a set of template parameters of the one pass kernel.
 //   n <= 4096 uses a single-workgroup-per-column LDS kernel.
 #include <stdlib.h>
 #include <string.h>
@@ -173,6 +176,48 @@ __host__ __device__ constexpr int brev_c(int x, int bits)
     return r;
 }
 
+// What a launch of the pass kernel is, fixed at compile time so that each
+// instantiation keeps only its own state in registers:
+//   ROLE  non-last pass with its outer twiddles from the table, non-last pass
+//         with recurrence outer twiddles, or last pass (digit-reversed scatter)
+//   IN    (non-last; the last pass of >= 2 always reads a full intermediate)
+//         the input is full, or exactly its rows j1 >= R1/2 are zero padding
+//         (forward, first pass of the LDE: those rows are not loaded), or
+//         rows >= src_valid are zero (any other padding: a compare per load)
+//   POST  (last) no factor, one factor for all rows, or the per-row tables
+enum : int { ROLE_TAB = 0, ROLE_REC = 1, ROLE_LAST = 2 };
+enum : int { IN_FULL = 0, IN_HALF = 1, IN_CHECK = 2 };
+enum : int { POST_NONE = 0, POST_SCALE = 1, POST_TABLE = 2 };
+
+// Element at a 32-bit byte offset (a lane's, in a VGPR) from a wave-uniform
+// base (the column pointer plus the tile's base, in SGPRs): one global access
+// with no 64-bit VALU address arithmetic.  A column is at most 2^28 words.
+// The base passes through an empty asm with an SGPR constraint: left visible,
+// the optimizer folds a uniform row stride into the lane's offset and is back
+// at one 64-bit VALU address per access.
+template <class T>
+__device__ __forceinline__ T *sgpr_ptr(T *p)
+{
+    asm("" : "+s"(p));
+    return p;
+}
+// (behind the asm the pointer's address space is unknown: cast to global)
+#define ZK_GLOBAL __attribute__((address_space(1)))
+__device__ __forceinline__ uint64_t ld_off(const uint64_t *base, uint32_t byte_off)
+{
+    return *(const ZK_GLOBAL uint64_t *)((const ZK_GLOBAL char *)sgpr_ptr(base) + byte_off);
+}
+__device__ __forceinline__ void st_off(uint64_t *base, uint32_t byte_off, uint64_t x)
+{
+    *(ZK_GLOBAL uint64_t *)((ZK_GLOBAL char *)sgpr_ptr(base) + byte_off) = x;
+}
+
+// Outer-twiddle loads in flight ahead of their products (k_ntt_pass, step 2).
+// LDE 2^23 -> 2^24 x 100, three runs each on one box: 4 -> 65.2-66.1 Gelem/s,
+// R2 / 2 -> 65.1-65.3, R2 (82 VGPRs in the radix-256 pass) -> 64.9-65.1;
+// 0, a load in front of each product, 60.5-62.2.
+constexpr int NTT_OTW_AHEAD = 4;
+
 // One pass of radix R = 2^(L1+L2) over 16 independent sub-DFTs per workgroup.
 //   step 1: thread (g, j2) loads x[R2*j1 + j2] (j1 < R1), R1-point DFT in
 //           registers, times omega_R^(j2*k1), to LDS
@@ -182,11 +227,13 @@ __host__ __device__ constexpr int brev_c(int x, int bits)
 // SPLIT: the LDS transpose moves the low and then the high 32-bit words
 // through a half-size image (two more barriers), halving the workgroup's LDS
 // so more waves fit per CU (LDS, not VGPRs, limits the radix-256 pass).
-template <int L1, int L2, bool INV, bool SPLIT>
+template <int L1, int L2, bool INV, bool SPLIT, int ROLE, int IN, int POST>
 __global__ void __launch_bounds__(16 * (1 << L2)) k_ntt_pass(PassArgs a)
 {
     constexpr int R1 = 1 << L1, R2 = 1 << L2, LOGR = L1 + L2, R = 1 << LOGR;
     constexpr int T = GROUPS * R2;
+    constexpr bool LAST = ROLE == ROLE_LAST;
+    static_assert(!(LAST && IN != IN_FULL) && !(!LAST && POST != POST_NONE) && !(INV && IN == IN_HALF), "role");
     __shared__ uint64_t lds[SPLIT ? R * 8 : R * 17];
     uint32_t *lds32 = reinterpret_cast<uint32_t *>(lds);
     // SPLIT image: row rho = k1 * R2 + j2 holds the 16 groups' words; row
@@ -196,59 +243,55 @@ __global__ void __launch_bounds__(16 * (1 << L2)) k_ntt_pass(PassArgs a)
 
     __shared__ uint64_t twR[R];  // omega_R^i
     // columns vary fastest across workgroups: the workgroups sharing a unit's
-    // outer-twiddle slice run together and find it in L2
-    const uint32_t col = blockIdx.x % a.ncols;
-    const uint64_t u = blockIdx.x / a.ncols;
+    // outer-twiddle slice run together and find it in L2.  The quotient comes
+    // out of the VALU: back to SGPRs, so that every base below is scalar
+    const uint32_t col = __builtin_amdgcn_readfirstlane(blockIdx.x % a.ncols);
+    const uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x / a.ncols);
     const uint64_t *src = a.src + (uint64_t)col * a.src_ld;
     uint64_t *dst = a.dst + (uint64_t)col * a.dst_ld;
     const int tid = threadIdx.x;
 
     // omega_R^i = omega_4096^(i << (12 - LOGR)) (R <= 256)
     static_assert(LOGR <= 12, "radix");
-    if (a.rt4096)
-        for (int i = tid; i < R; i += T) twR[i] = a.rt4096[i << (12 - LOGR)];
-    else
-        for (int i = tid; i < R; i += T) twR[i] = tw_big(a.tw_lo, a.tw_hi, (uint64_t)i << (TW_MAX_LOG - LOGR));
+    for (int i = tid; i < R; i += T) twR[i] = a.rt4096[i << (12 - LOGR)];
 
     uint64_t v[R2 > R1 ? R2 : R1];
     // ------------------------------------------------ step 1 (load + R1-DFT)
+    // wave-uniform: base (the tile's first element), j0, k1g, rest
     int g, j2;
-    uint64_t base = 0, k1g = 0, rest = 0;
-    uint32_t logmp = 0, logS = 0;
-    if (!a.last) {
+    uint64_t base = 0;
+    uint32_t j0 = 0, k1g = 0, rest = 0, logmp = 0, logS = 0;
+    if constexpr (!LAST) {
         g = tid & 15;
         j2 = tid >> 4;
         logmp = a.logm - LOGR;
-        const uint64_t groups_per_blk = 1ULL << (logmp - 4);
-        const uint64_t blk = u >> (logmp - 4);
-        const uint64_t j0 = (u & (groups_per_blk - 1)) << 4;
-        base = (blk << a.logm) + j0;
+        const uint32_t blk = u >> (logmp - 4);
+        j0 = (u & ((1u << (logmp - 4)) - 1)) << 4;
+        base = ((uint64_t)blk << a.logm) + j0;
+        const uint64_t rstride = (uint64_t)R2 << logmp;  // elements between rows j1, j1 + 1
+        const uint32_t off = ((uint32_t)j2 << logmp) + g;
+        const uint64_t *s = src + base;
 #pragma unroll
-        for (int j1 = 0; j1 < R1; j1++) {
-            uint64_t pos = base + ((uint64_t)(R2 * j1 + j2) << logmp) + g;
-            v[j1] = pos < a.src_valid ? src[pos] : 0;
+        for (int j1 = 0; j1 < (IN == IN_HALF ? R1 / 2 : R1); j1++) {
+            if constexpr (IN == IN_CHECK)
+                v[j1] = base + j1 * rstride + off < a.src_valid ? ld_off(s + j1 * rstride, off * 8) : 0;
+            else
+                v[j1] = ld_off(s + j1 * rstride, off * 8);
         }
     } else {
         j2 = tid & (R2 - 1);
         g = tid >> L2;
         logS = a.logn - a.rbits[0] - LOGR;
-        rest = u & ((1ULL << logS) - 1);
+        rest = u & ((1u << logS) - 1);
         k1g = u >> logS;
-        const uint64_t blk = ((k1g * 16 + g) << logS) + rest;
+        // x[(((k1g * 16 + g) << logS) + rest) << LOGR | R2 * j1 + j2]
+        const uint64_t *s = src + (((((uint64_t)k1g * 16) << logS) + rest) << LOGR);
+        const uint32_t off = ((uint32_t)g << (logS + LOGR)) + j2;
 #pragma unroll
-        for (int j1 = 0; j1 < R1; j1++) {
-            uint64_t pos = (blk << LOGR) + R2 * j1 + j2;
-            v[j1] = pos < a.src_valid ? src[pos] : 0;
-        }
+        for (int j1 = 0; j1 < R1; j1++) v[j1] = ld_off(s + R2 * j1, off * 8);
     }
-    if constexpr (!INV) {
-        if (a.half_zero)
-            dft_regs_half<L1, INV, true>(v);
-        else
-            dft_regs<L1, INV, true>(v);
-    } else {
-        dft_regs<L1, INV, true>(v);
-    }
+    if constexpr (IN == IN_HALF) dft_regs_half<L1, INV, true>(v);
+    else dft_regs<L1, INV, true>(v);
     __syncthreads();  // twR ready
 #pragma unroll
     for (int r = 0; r < R1; r++) {
@@ -295,35 +338,53 @@ __global__ void __launch_bounds__(16 * (1 << L2)) k_ntt_pass(PassArgs a)
     // ------------------------------------------------ step 2 (R2-DFT + store)
     g = g2;
     const int k1 = k1s;
+    // table outer twiddles: X[k] * omega_m^(j' k), k = k1 + R1*k2, j' = j0 + g;
+    // the table entry (k << logmp) + j' and the output base + (k << logmp) + g
+    // share the lane's offset.  The first OTW_AHEAD loads are issued here, in
+    // front of the R2-point DFT, and each later one OTW_AHEAD products ahead
+    // of its use: the butterflies' and products' rare-correction branches end
+    // a basic block each, and a load left between them is issued, waited for
+    // and used on the spot (R2 memory round trips per thread, one after the
+    // other).
+    constexpr int OTW_AHEAD = ROLE != ROLE_TAB ? 0 : NTT_OTW_AHEAD < R2 ? NTT_OTW_AHEAD : R2;
+    uint64_t w[R2];
+    const uint64_t kstride_t = (uint64_t)R1 << logmp;  // elements between k2, k2 + 1
+    const uint32_t off_t = (((uint32_t)k1 << logmp) + g) * 8;
+    const uint64_t *ot = a.otw + j0;
+    if constexpr (ROLE == ROLE_TAB) {
+#pragma unroll
+        for (int k2 = 0; k2 < OTW_AHEAD; k2++) w[k2] = ld_off(ot + k2 * kstride_t, off_t);
+    }
     dft_regs<L2, INV, true>(v);
-    if (!a.last && a.otw) {
-        // X[k] * omega_m^(j' k) from the table (one coalesced load per element
-        // instead of a recurrence product), k = k1 + R1*k2, j' = j0 + g
-        const uint64_t jp = (base & ((1ULL << logmp) - 1)) + g;
+    if constexpr (ROLE == ROLE_TAB) {
+        uint64_t *d = dst + base;
 #pragma unroll
         for (int k2 = 0; k2 < R2; k2++) {
             const int r = brev_c(k2, L2);
-            const uint64_t k = (uint64_t)(k1 + R1 * k2);
             uint64_t x = v[r];
-            if (k1 | k2) x = gl_mul_rb(x, a.otw[(k << logmp) + jp]);
-            dst[base + (k << logmp) + g] = x;  // intermediate: lazy
+            if (k1 | k2) x = gl_mul_rb(x, w[k2]);
+            if (k2 + OTW_AHEAD < R2) w[k2 + OTW_AHEAD] = ld_off(ot + (k2 + OTW_AHEAD) * kstride_t, off_t);
+            st_off(d + k2 * kstride_t, off_t, x);  // intermediate: lazy
         }
-    } else if (!a.last) {
+    } else if constexpr (ROLE == ROLE_REC) {
         // X[k] * omega_m^(j' k), k = k1 + R1*k2, j' = j0 + g
         const uint32_t tshift = TW_MAX_LOG - a.logm;
-        const uint64_t jp = (base & ((1ULL << logmp) - 1)) + g;
+        const uint64_t jp = (uint64_t)j0 + g;
         uint64_t t = tw_big(a.tw_lo, a.tw_hi, (jp * k1) << tshift);
         const uint64_t step = tw_big(a.tw_lo, a.tw_hi, (jp * R1) << tshift);
+        const uint64_t kstride = (uint64_t)R1 << logmp;
+        const uint32_t off = (((uint32_t)k1 << logmp) + g) * 8;
+        uint64_t *d = dst + base;
 #pragma unroll
         for (int k2 = 0; k2 < R2; k2++) {
             const int r = brev_c(k2, L2);
             uint64_t x = v[r];
             if (k1 | k2) x = gl_mul(x, t);
-            dst[base + ((uint64_t)(k1 + R1 * k2) << logmp) + g] = x;  // intermediate: lazy
+            st_off(d + k2 * kstride, off, x);  // intermediate: lazy
             t = gl_mul(t, step);
         }
     } else {
-        uint64_t rrev = 0;
+        uint32_t rrev = 0;
         {
             // rest = sum_{i=1..npass-2} k_i * prod_{l>i} r_l; rrev = mixed-radix reversal
             uint32_t rev_pos[NTT_MAX_PASSES];
@@ -332,25 +393,31 @@ __global__ void __launch_bounds__(16 * (1 << L2)) k_ntt_pass(PassArgs a)
                 rev_pos[i] = acc;
                 acc += a.rbits[i];
             }
-            uint64_t rr = rest;
+            uint32_t rr = rest;
             for (int i = (int)a.npass - 2; i >= 1; i--) {
-                uint64_t d = rr & ((1ULL << a.rbits[i]) - 1);
+                uint32_t d = rr & ((1u << a.rbits[i]) - 1);
                 rr >>= a.rbits[i];
                 rrev |= d << rev_pos[i];
             }
         }
+        // row x0 + ((R1 * k2) << lognr), x0 = ub + lane offset (< n <= 2^28)
         const uint32_t lognr = a.logn - LOGR;
-        const uint64_t x0 = (k1g * 16 + g) + (rrev << a.rbits[0]) + ((uint64_t)k1 << lognr);
-        const bool scaled = a.post_lo != nullptr || a.post_scale != 1;
+        const uint32_t ub = k1g * 16 + (rrev << a.rbits[0]);
+        const uint32_t xoff = (uint32_t)g + ((uint32_t)k1 << lognr);
+        const uint64_t kstride = (uint64_t)R1 << lognr;
+        uint64_t *d = dst + ub;
         uint64_t f = a.post_scale;
-        if (a.post_lo) f = gl_mul(a.post_lo[x0 & ((1ULL << a.post_bits) - 1)], a.post_hi[x0 >> a.post_bits]);
+        if constexpr (POST == POST_TABLE) {
+            const uint32_t x0 = ub + xoff;
+            f = gl_mul(a.post_lo[x0 & (uint32_t)((1ULL << a.post_bits) - 1)], a.post_hi[x0 >> a.post_bits]);
+        }
 #pragma unroll
         for (int k2 = 0; k2 < R2; k2++) {
             const int r = brev_c(k2, L2);
             uint64_t x = v[r];
-            if (scaled) x = gl_mul(x, f);
-            dst[x0 + ((uint64_t)(R1 * k2) << lognr)] = gl_canon(x);
-            if (a.post_lo) f = gl_mul(f, a.post_step);
+            if constexpr (POST != POST_NONE) x = gl_mul(x, f);
+            st_off(d + k2 * kstride, xoff * 8, gl_canon(x));
+            if constexpr (POST == POST_TABLE) f = gl_mul(f, a.post_step);
         }
     }
 }
@@ -517,16 +584,48 @@ static void split_radix(uint32_t logn, uint32_t *npass, uint32_t rbits[NTT_MAX_P
     for (uint32_t i = 0; i < P; i++) rbits[i] = base + (i >= P - extra ? 1 : 0);
 }
 
+template <int L1, int L2, bool INV, int ROLE, int IN, int POST>
+static void launch_inst(const PassArgs &a, dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_ntt_pass<L1, L2, INV, true, ROLE, IN, POST>), grid, dim3(16 << L2), 0, s, a);
+}
+
+// the instantiation of this launch: role from a.last / a.otw, input from
+// a.half_zero / a.src_valid, post-scale from a.post_lo / a.post_scale
+template <int L1, int L2, bool INV>
+static void launch_role(const PassArgs &a, dim3 grid, hipStream_t s)
+{
+    if (a.last) {
+        if (a.post_lo) launch_inst<L1, L2, INV, ROLE_LAST, IN_FULL, POST_TABLE>(a, grid, s);
+        else if (a.post_scale != 1) launch_inst<L1, L2, INV, ROLE_LAST, IN_FULL, POST_SCALE>(a, grid, s);
+        else launch_inst<L1, L2, INV, ROLE_LAST, IN_FULL, POST_NONE>(a, grid, s);
+        return;
+    }
+    const bool full = a.src_valid >= (1ULL << a.logn);
+    if constexpr (!INV) {
+        if (a.half_zero) {
+            if (a.otw) launch_inst<L1, L2, INV, ROLE_TAB, IN_HALF, POST_NONE>(a, grid, s);
+            else launch_inst<L1, L2, INV, ROLE_REC, IN_HALF, POST_NONE>(a, grid, s);
+            return;
+        }
+    }
+    if (full) {
+        if (a.otw) launch_inst<L1, L2, INV, ROLE_TAB, IN_FULL, POST_NONE>(a, grid, s);
+        else launch_inst<L1, L2, INV, ROLE_REC, IN_FULL, POST_NONE>(a, grid, s);
+    } else {
+        if (a.otw) launch_inst<L1, L2, INV, ROLE_TAB, IN_CHECK, POST_NONE>(a, grid, s);
+        else launch_inst<L1, L2, INV, ROLE_REC, IN_CHECK, POST_NONE>(a, grid, s);
+    }
+}
+
 template <int L1, int L2>
 static void launch_pass(const PassArgs &a, uint64_t ncols, int inverse, hipStream_t s)
 {
     constexpr int LOGR = L1 + L2;
     uint64_t units = (1ULL << (a.logn - LOGR)) / 16;
     dim3 grid((uint32_t)(units * ncols));
-    if (inverse)
-        hipLaunchKernelGGL((k_ntt_pass<L1, L2, true, true>), grid, dim3(16 << L2), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_ntt_pass<L1, L2, false, true>), grid, dim3(16 << L2), 0, s, a);
+    if (inverse) launch_role<L1, L2, true>(a, grid, s);
+    else launch_role<L1, L2, false>(a, grid, s);
 }
 
 static void dispatch_pass(uint32_t logr, const PassArgs &a, uint64_t ncols, int inverse, hipStream_t s)
