@@ -548,6 +548,35 @@ uint64_t zkgpu_multiset_diff_workspace_bytes(uint64_t n);
 int zkgpu_multiset_diff_dev(uint64_t *out, const uint64_t *a, uint64_t a_ld, const uint64_t *b, uint64_t b_ld,
                             uint64_t n, uint32_t dim, uint32_t max_vals);
 
+/* The values of a plookup's source column f that no row of its table column t holds (the
+ * prover's trace audit, include/zkgpu_stark.h zkgpu_stark_audit: calculateH1H2 stops at the first
+ * such row, "Number not included"; this lists all of them).  Columns, values and dim as for
+ * zkgpu_multiset_diff_dev: dim 1 or 3 with the components one leading dimension apart, a value is
+ * the canonical dim-tuple (v and v + p are the same value).
+ * out (device, 2 + 2 * max_vals words):
+ *   out[0]  rows i < n of f whose value no row of t holds
+ *   out[1]  distinct such values
+ *   then max_vals pairs {the value's first row in f, its count in f}, ascending by that row;
+ *   {UINT64_MAX, 0} past the last
+ * One wrong value repeated on a million rows is ONE entry with count 1000000.
+ * The result does not depend on the launch geometry or on which thread claims a table slot: the
+ * table is the multiset difference's over f and t (counts are atomic sums, first rows atomic
+ * minima), out[0] is the sum of the missing values' counts (added up per workgroup before one
+ * atomic each), and the list comes from the reduction of zkgpu_nonzero_rows_dev over a flag on
+ * each missing value's first row.  Enqueued on the library stream, no host synchronisation; rows
+ * [n, ld) are not read; f == t is allowed.  ZKGPU_ERR_ARG, nothing queued: f_ld < n or t_ld < n,
+ * dim not 1 or 3, max_vals > 4096, n > 2^28, null pointers; n = 0 writes two zero counts and a
+ * padded list.
+ * Scratch: the grow-only workspace of the plookup and the multiset difference, of
+ *   zkgpu_lookup_misses_workspace_bytes(n) = 16 m + 8 n + 8 ceil(ceil(n / 1024) / 2) + 8 * 4097 + 8
+ * bytes, m = the smallest power of two >= 4 n (0 for n = 0): the same table, one n-row flag
+ * column, the reduction's block counts, one row list and the word out[0] adds up in -- never more
+ * than zkgpu_multiset_diff_workspace_bytes(n), so one allocation serves both (host only, no GPU
+ * needed). */
+uint64_t zkgpu_lookup_misses_workspace_bytes(uint64_t n);
+int zkgpu_lookup_misses_dev(uint64_t *out, const uint64_t *f, uint64_t f_ld, const uint64_t *t, uint64_t t_ld,
+                            uint64_t n, uint32_t dim, uint32_t max_vals);
+
 /* 3 ext columns (ld >= n) -> interleaved n x 3 (the FRI polynomial layout, friProve.cpp) */
 int zkgpu_cols3_to_interleaved_dev(uint64_t *out, const uint64_t *cols, uint64_t ld, uint64_t n);
 

@@ -296,6 +296,79 @@ typedef struct {
 } zkgpu_z_diag;
 int zkgpu_stark_z_diag(void *handle, zkgpu_z_diag *out);
 
+/* ---- trace audit: every broken plookup, product and identity of a loaded trace, no proof
+ * The diagnoses above run inside a proof and end it at the first finding: stage 1's LDE and tree
+ * come first, the first plookup with a miss or the lowest open product is the last thing the
+ * proof says.  The audit runs the stage-2 and stage-3 work of a proof on the n domain and nothing
+ * else -- no LDE, no tree, no stage 4 or 5, no FRI, nothing committed -- to the end, and reports
+ * everything it finds in one call.
+ *
+ * NOT A VERIFIER.  With no roots to draw from, the audit's challenges come from a transcript that
+ * holds the verkey and the publics only: ch0 .. ch3 are its first four getField, the combination
+ * challenge the fifth.  They are not the proof's challenges and do not depend on the trace, so a
+ * trace built on purpose could be fitted to them: the audit is an aid against executor bugs, not
+ * a soundness check.  Rows, counts, first rows and term ids do not depend on the challenges (with
+ * overwhelming probability); the values at the failing rows do.
+ *
+ *   A  plookups, every one of n_pu: step2, then calculateH1H2 per plookup.  Where it reports a
+ *      miss the plookup's h1 / h2 columns of cm2_n are zeroed, zkgpu_lookup_misses_dev
+ *      (include/zkgpu.h) lists the f values its table does not hold, and the audit goes on to the
+ *      next plookup.  The lowest ZKGPU_AUDIT_MAX_PU failing plookups are detailed, all are counted.
+ *   B  grand products, every one of n_zctx: step3prev, then calculateZ (which writes every z
+ *      column whether or not its product closes).  Each of the lowest ZKGPU_AUDIT_MAX_Z open
+ *      products has its num and den columns compared as multisets (zkgpu_multiset_diff_dev, the
+ *      lists of zkgpu_z_diag; compared = 0 when the scratch could not be allocated: the product is
+ *      still listed).  A plookup that missed leaves its own product open (its h1 / h2 read zero):
+ *      that entry follows from layer A's and says nothing new.
+ *   C  identities: the post-Z step3 program, then the constraint combination on the n domain with
+ *      the audit's challenge (the constraint check above; the first use rewrites step42ns as
+ *      check_set does), with ZKGPU_AUDIT_NAMES also the terms at the failing rows (as
+ *      check_names_set; a combination the split refuses degrades to rows only).  An open product
+ *      does not stop it: its boundary identity fails on a row or two and the names say which.  A
+ *      plookup that missed does: h1 / h2 are meaningless and C would fail on almost every row --
+ *      identities.ran = 0 then, as for a step42ns the n-domain rewrite refuses (layers A and B
+ *      still run; zkgpu_stark_audit_format says which it was).
+ *
+ * A dirty trace is not a failed call: audit returns 0 whenever it ran to the end and `clean`
+ * carries the verdict.  Refused, with a message: a sharded handle (single-GPU provers only), no
+ * whole trace loaded (before any set_cm1 / witness, after a failed streamed load, under the lean
+ * plan after a proof consumed the trace).
+ * Afterwards: the trace is untouched and not consumed under either plan -- prove() may follow
+ * directly and gives the proof it would have given; a pending set_cm1_async load is left alone; no
+ * probe records are taken; check_set's mode and check_names_set's are neither consulted nor
+ * changed.  zkgpu_stark_check_result / check_terms / check_named and zkgpu_stark_z_diag (the lowest
+ * open product, or ran = 0) refer to the audit as the latest run; zkgpu_stark_timers gives AUDIT_*
+ * lines (AUDIT_STEP2, AUDIT_H1H2, AUDIT_STEP3PREV, AUDIT_Z, AUDIT_STEP3, AUDIT_CONSTRAINTS,
+ * AUDIT_TOTAL).  One synchronisation per layer.  Nothing is added to a memory plan: the scratch
+ * is the library workspace and result blocks allocated when a finding needs them. */
+#define ZKGPU_AUDIT_NAMES 1u      /* flags: also evaluate the terms of the combination at the failing rows */
+#define ZKGPU_AUDIT_MAX_PU 8
+#define ZKGPU_AUDIT_MAX_Z 8
+#define ZKGPU_LOOKUP_MISS_MAX 16
+typedef struct { uint64_t row, count; } zkgpu_lookup_miss;
+typedef struct {
+    uint32_t pu;              /* index into pu */
+    uint64_t n_rows, n_vals;  /* rows of f whose value the table does not hold; distinct such values */
+    zkgpu_lookup_miss vals[ZKGPU_LOOKUP_MISS_MAX]; /* {first row in f, rows in f}, by row; {UINT64_MAX, 0} past the last */
+} zkgpu_audit_pu;
+typedef struct {
+    uint32_t z, compared;     /* index into zctx; 1: the lists below are filled */
+    uint64_t n_num, n_den;
+    zkgpu_z_diag_val num[ZKGPU_Z_DIAG_MAX], den[ZKGPU_Z_DIAG_MAX];
+} zkgpu_audit_z;
+typedef struct {
+    uint32_t clean;                 /* 1: no layer found anything */
+    uint64_t challenges[15];        /* the audit's own: ch0..ch3 and the combination challenge */
+    uint32_t n_pu_bad;  zkgpu_audit_pu pu[ZKGPU_AUDIT_MAX_PU];   /* the lowest failing plookups */
+    uint32_t n_z_open;  zkgpu_audit_z  z[ZKGPU_AUDIT_MAX_Z];     /* the lowest open products */
+    zkgpu_check_result identities;  /* ran = 0 when a plookup missed (above) */
+} zkgpu_audit_report;
+int zkgpu_stark_audit(void *handle, uint32_t flags, zkgpu_audit_report *out);
+/* the report of the last audit as text, one finding per line in the wording of the proof's failure
+ * messages; returns the length the whole text needs (without the terminator), at most len - 1
+ * characters are written; fails when no audit has run on the handle */
+int zkgpu_stark_audit_format(void *handle, char *buf, uint64_t len);
+
 /* ---- the Fiat-Shamir transcript the prover runs on the host, as the
  * reference's class Transcript (transcript.hpp:14-37, transcript.cpp:4-88):
  * Poseidon-GL sponge, 8-element rate, 4-element capacity.  Host code only

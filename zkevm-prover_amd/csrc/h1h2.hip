@@ -18,6 +18,7 @@
 // round-2 form: 8.1 against 1.9 ms for two plookups at 2^23.)
 #include <stdlib.h>
 
+#include <algorithm>
 #include <vector>
 
 #include <rocprim/device/device_scan.hpp>
@@ -753,7 +754,157 @@ int multiset_diff(uint64_t *out, const uint64_t *a, uint64_t a_ld, const uint64_
     return check_launch("multiset_diff");
 }
 
+// ---------------------------------------------------------------- lookup misses
+// The f values of a plookup that no row of its table t holds (the prover's
+// trace audit; include/zkgpu.h zkgpu_lookup_misses_dev).  The table is the
+// multiset table above over a = f and b = t (k_ms_insert as it stands): a value
+// misses iff its slot ends with cntb = 0, its slot is then its first row in f
+// and cnta its rows there.  k_lookup_flag walks the slots once: it flags the
+// first row of every missing value and adds up their cnta -- the rows that
+// miss -- per thread, then per wave and workgroup, so that one atomic per
+// workgroup reaches the global sum (a sum of integers: the grid does not
+// change it).  The nonzero-rows reduction lists the lowest max_vals flagged
+// rows and counts all of them (the distinct values); k_lookup_emit looks each
+// listed row's count up again.
+constexpr uint32_t LM_FLAG_BLOCKS = 1024;  // grid-stride cap of k_lookup_flag
+
+__global__ void __launch_bounds__(256) k_lookup_flag(uint64_t *flag, unsigned long long *n_rows, MsTable T)
+{
+    __shared__ uint32_t part[4];
+    // a thread's sum is part of the sum of all cnta = n <= 2^28: u32 holds it
+    uint32_t sum = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= T.mask; k += stride) {
+        const uint32_t g = T.slot[k];
+        if (g == H12_EMPTY || g >= T.n || T.cntb[k]) continue;  // empty, a value of t only, or a value t holds
+        flag[g] = 1;
+        sum += T.cnta[k];
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) sum += (uint32_t)__shfl_down((int)sum, off);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t tot = part[0] + part[1] + part[2] + part[3];
+        if (tot) atomicAdd(n_rows, (unsigned long long)tot);
+    }
+}
+
+// out = {rows that miss, distinct values, then per listed row {row, its value's rows in f}}
+template <int DIM>
+__global__ void __launch_bounds__(256) k_lookup_emit(uint64_t *out, const uint64_t *list,
+                                                     const unsigned long long *n_rows, uint32_t max_vals, MsTable T)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k == 0) {
+        out[0] = *n_rows;
+        out[1] = list[0];
+    }
+    if (k >= max_vals) return;
+    const uint64_t row = list[1 + k];
+    uint64_t cnt = 0;
+    if (row < T.n) {
+        uint64_t key[DIM];
+        h12_key<DIM>(key, T.a, T.a_ld, row);
+        uint64_t h = h12_hash<DIM>(key) & T.mask;
+        for (uint64_t probe = 0; probe <= T.mask; probe++, h = (h + 1) & T.mask) {
+            const uint32_t cur = T.slot[h];
+            if (cur == H12_EMPTY) break;
+            if (ms_eq<DIM>(T, cur, key)) {
+                cnt = T.cnta[h];
+                break;
+            }
+        }
+    }
+    out[2 + 2ULL * k] = row;  // (the reduction pads its list with UINT64_MAX)
+    out[3 + 2ULL * k] = cnt;
+}
+
+// the layout of the workspace (include/zkgpu.h states the sum): the multiset
+// table, ONE flag column and list, and the word the missing rows add up in
+struct LmLayout {
+    uint64_t m, table, flags, counts, list, sum, total;
+};
+static LmLayout lm_layout(uint64_t n)
+{
+    LmLayout L;
+    L.m = ms_table_size(n);
+    L.table = 0;
+    L.flags = L.table + 16 * L.m;
+    L.counts = L.flags + 8 * n;
+    L.list = L.counts + 8 * (((uint64_t)nonzero_rows_blocks(n) + 1) / 2);
+    L.sum = L.list + 8 * (1 + (uint64_t)MS_MAX_VALS);
+    L.total = L.sum + 8;
+    return L;
+}
+
+uint64_t lookup_misses_workspace_bytes(uint64_t n) { return lm_layout(n).total; }
+
+int lookup_misses(uint64_t *out, const uint64_t *f, uint64_t f_ld, const uint64_t *t, uint64_t t_ld, uint64_t n,
+                  uint32_t dim, uint32_t max_vals, hipStream_t s)
+{
+    const LmLayout L = lm_layout(n);
+    char *w = (char *)workspace(4, L.total);
+    if (!w) return ZKGPU_ERR_OOM;
+    MsTable T;
+    T.slot = (uint32_t *)(w + L.table);
+    T.firstb = T.slot + L.m;
+    T.cnta = T.firstb + L.m;
+    T.cntb = T.cnta + L.m;
+    T.mask = L.m - 1;
+    T.a = f, T.b = t, T.a_ld = f_ld, T.b_ld = t_ld, T.n = n;
+    uint64_t *flag = (uint64_t *)(w + L.flags);
+    uint32_t *counts = (uint32_t *)(w + L.counts);
+    uint64_t *list = (uint64_t *)(w + L.list);
+    unsigned long long *sum = (unsigned long long *)(w + L.sum);
+    const uint32_t B = 256;
+    if (check_hip(hipMemsetAsync(sum, 0, 8, s), "lookup_misses memset")) return ZKGPU_ERR_HIP;
+    if (n) {
+        prof_begin(s);
+        // slot and firstb empty, the counts and the flags zero
+        if (check_hip(hipMemsetAsync(T.slot, 0xFF, 8 * L.m, s), "lookup_misses memset") ||
+            check_hip(hipMemsetAsync(T.cnta, 0, 8 * L.m + 8 * n, s), "lookup_misses memset"))
+            return ZKGPU_ERR_HIP;
+        if (dim == 1)
+            hipLaunchKernelGGL(k_ms_insert<1>, dim3(nblk2(2 * n, B)), dim3(B), 0, s, T);
+        else
+            hipLaunchKernelGGL(k_ms_insert<3>, dim3(nblk2(2 * n, B)), dim3(B), 0, s, T);
+        prof_end("k_multiset_insert", (double)dim * 8.0 * 2.0 * n, s);
+        prof_begin(s);
+        hipLaunchKernelGGL(k_lookup_flag, dim3(std::min(nblk2(L.m, B), LM_FLAG_BLOCKS)), dim3(B), 0, s, flag, sum, T);
+        prof_end("k_lookup_flag", 12.0 * (double)L.m, s);
+        if (check_launch("lookup_misses")) return ZKGPU_ERR_HIP;
+    }
+    int rc;
+    if ((rc = nonzero_rows(list, counts, flag, n, 1, n, max_vals, s))) return rc;
+    prof_begin(s);
+    if (dim == 1)
+        hipLaunchKernelGGL(k_lookup_emit<1>, dim3(nblk2(max_vals ? max_vals : 1, B)), dim3(B), 0, s, out, list, sum,
+                           max_vals, T);
+    else
+        hipLaunchKernelGGL(k_lookup_emit<3>, dim3(nblk2(max_vals ? max_vals : 1, B)), dim3(B), 0, s, out, list, sum,
+                           max_vals, T);
+    prof_end("k_lookup_emit", 8.0 * (2 + 2.0 * max_vals), s);
+    return check_launch("lookup_misses");
+}
+
 }  // namespace zk
+
+// the C-ABI of the lookup misses (include/zkgpu.h), beside its kernels
+extern "C" uint64_t zkgpu_lookup_misses_workspace_bytes(uint64_t n) { return zk::lookup_misses_workspace_bytes(n); }
+
+extern "C" int zkgpu_lookup_misses_dev(uint64_t *out, const uint64_t *f, uint64_t f_ld, const uint64_t *t,
+                                       uint64_t t_ld, uint64_t n, uint32_t dim, uint32_t max_vals)
+{
+    if (!zk::ctx().ready) return zk::set_error(ZKGPU_ERR_INIT, "zkgpu_init() not called");
+    if (!out || (n && (!f || !t))) return zk::set_error(ZKGPU_ERR_ARG, "lookup_misses: null pointer");
+    if (dim != 1 && dim != 3) return zk::set_error(ZKGPU_ERR_ARG, "lookup_misses: dim must be 1 or 3");
+    if (max_vals > zk::MS_MAX_VALS)
+        return zk::set_error(ZKGPU_ERR_ARG, "lookup_misses: max_vals %u > %u", max_vals, zk::MS_MAX_VALS);
+    if (n > (1ULL << 28)) return zk::set_error(ZKGPU_ERR_ARG, "lookup_misses: more than 2^28 rows");
+    if (f_ld < n || t_ld < n) return zk::set_error(ZKGPU_ERR_ARG, "lookup_misses: ld < n");
+    return zk::lookup_misses(out, f, f_ld, t, t_ld, n, dim, max_vals, zk::ctx().stream);
+}
 
 // the C-ABI of the multiset difference (include/zkgpu.h), beside its kernels
 extern "C" uint64_t zkgpu_multiset_diff_workspace_bytes(uint64_t n) { return zk::multiset_diff_workspace_bytes(n); }

@@ -22,7 +22,7 @@
 // step52ns), run as GPU programs (ProverInfo, host/stark_info.cpp); for the
 // zkEVM's parser bytecode, StepsGPU (host/zkgpu_steps.hpp) is the binding.
 //
-// Usage: zkgpu_batch_prover [--stream-trace] [--check-trace] [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]]
+// Usage: zkgpu_batch_prover [--stream-trace] [--check-trace] [--audit] [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]]
 //                           <config.json>
 //        (--stream-trace: the trace file's rows stay in host memory and cross
 //        PCIe under stage 1 of the proof, zkgpu_stark_prove_from_rows; single GPU)
@@ -31,6 +31,12 @@
 //        commit with the first such row in the message and the terms of the
 //        constraint combination that fail there (zkgpu_stark_check_names_set),
 //        a non-zero status and no proof files; single GPU)
+//        (--audit: no proof.  The trace audit, zkgpu_stark_audit with naming on: every plookup
+//        with values its table does not hold, every grand product that does not close and,
+//        unless a plookup missed, every row that breaks an identity, each with its starkinfo
+//        context; the report on stdout and in <outputPath>/trace_audit.json, no proof file;
+//        status 0 for a clean trace, 3 for one with findings.  Not a verifier: the audit's
+//        challenges do not depend on the trace (include/zkgpu_stark.h).  Single GPU)
 //        (--shard: one rank of ONE proof row-sharded over WORLD processes,
 //        zkgpu_stark_create_sharded; every rank runs this command with the
 //        same config, rank 0 writes the outputs.  rccl: rank 0 writes the
@@ -57,6 +63,7 @@
 
 #include "../../include/zkgpu.h"
 #include "../../include/zkgpu_stark.h"
+#include "zkgpu_audit_format.hpp"
 #include "zkgpu_fri_proof.hpp"
 #include "zkgpu_json.hpp"
 #include "zkgpu_stark_info.hpp"
@@ -139,7 +146,107 @@ struct Shard {
     int device = -1;
     bool stream_trace = false;  // --stream-trace: zkgpu_stark_prove_from_rows instead of set_cm1 + prove
     bool check_trace = false;   // --check-trace: zkgpu_stark_check_set(ZKGPU_CHECK_STOP)
+    bool audit = false;         // --audit: zkgpu_stark_audit instead of a proof
 };
+
+// --audit: the report as text (stdout) and as <dir>/trace_audit.json, the keys of zkgpu_audit_report
+// plus each finding's starkinfo context and, per listed failing row, the failing term ids.  The
+// driver's products come in the order puCtx, peCtx, ciCtx: product k < nPu is plookup k's.
+static int audit_trace(void *h, const zkgpu::StarkInfo &si, const zkgpu_stark_info &info, const std::string &dir)
+{
+    zkgpu_audit_report r;
+    if (zkgpu_stark_audit(h, ZKGPU_AUDIT_NAMES, &r)) throw std::runtime_error(std::string("audit: ") + zkgpu_stark_last_error());
+    zkgpu_host::AuditContext c;
+    c.n_bits = info.n_bits;
+    c.n_pu = info.n_pu;
+    c.n_zctx = info.n_zctx;
+    for (uint32_t k = 0; k < info.n_pu; k++) c.pu_label.push_back(si.z_context(k));
+    for (uint32_t z = 0; z < info.n_zctx; z++) {
+        c.z_label.push_back(si.z_context(z));
+        c.z_plookup.push_back(z < info.n_pu ? (int32_t)z : -1);
+    }
+    auto str = [](uint64_t v) { return Value::str(std::to_string(v % 0xFFFFFFFF00000001ULL)); };
+    Value j = Value::object();
+    j.set("clean", Value::num(r.clean));
+    Value ch = Value::array();
+    for (uint64_t v : r.challenges) ch.push(str(v));
+    j.set("challenges", ch);
+    j.set("n_pu_bad", Value::num(r.n_pu_bad));
+    Value pus = Value::array();
+    for (uint32_t k = 0; k < r.n_pu_bad && k < ZKGPU_AUDIT_MAX_PU; k++) {
+        const zkgpu_audit_pu &e = r.pu[k];
+        Value o = Value::object(), vals = Value::array();
+        o.set("pu", Value::num(e.pu));
+        o.set("context", Value::str(si.z_context(e.pu)));
+        o.set("n_rows", Value::num(e.n_rows));
+        o.set("n_vals", Value::num(e.n_vals));
+        for (const zkgpu_lookup_miss &m : e.vals) {
+            if (m.row == UINT64_MAX) break;
+            Value p = Value::array();
+            p.push(Value::num(m.row));
+            p.push(Value::num(m.count));
+            vals.push(p);
+        }
+        o.set("vals", vals);
+        pus.push(o);
+    }
+    j.set("pu", pus);
+    j.set("n_z_open", Value::num(r.n_z_open));
+    Value zs = Value::array();
+    for (uint32_t k = 0; k < r.n_z_open && k < ZKGPU_AUDIT_MAX_Z; k++) {
+        const zkgpu_audit_z &e = r.z[k];
+        Value o = Value::object();
+        o.set("z", Value::num(e.z));
+        o.set("context", Value::str(si.z_context(e.z)));
+        o.set("compared", Value::num(e.compared));
+        o.set("n_num", Value::num(e.n_num));
+        o.set("n_den", Value::num(e.n_den));
+        for (int side = 0; side < 2; side++) {
+            Value l = Value::array();
+            for (const zkgpu_z_diag_val &v : side ? e.den : e.num) {
+                if (v.row == UINT64_MAX) break;
+                Value t = Value::array();
+                t.push(Value::num(v.row));
+                t.push(Value::num(v.count_num));
+                t.push(Value::num(v.count_den));
+                l.push(t);
+            }
+            o.set(side ? "den" : "num", l);
+        }
+        zs.push(o);
+    }
+    j.set("z", zs);
+    Value id = Value::object(), rows = Value::array(), val = Value::array(), al = Value::array(), named = Value::array();
+    id.set("ran", Value::num(r.identities.ran));
+    id.set("n_bad", Value::num(r.identities.n_bad));
+    for (uint32_t s = 0; s < ZKGPU_CHECK_MAX_ROWS && r.identities.rows[s] != UINT64_MAX; s++) {
+        rows.push(Value::num(r.identities.rows[s]));
+        // the failing terms of the row (naming degrades to rows only when the split refuses the program)
+        uint32_t n = 0;
+        std::vector<uint32_t> ids(4096);
+        std::vector<uint64_t> vals(3 * ids.size());
+        if (!r.identities.ran || !r.identities.n_bad ||
+            zkgpu_stark_check_named(h, s, ids.data(), vals.data(), (uint32_t)ids.size(), &n))
+            continue;
+        c.named = true;
+        ids.resize(std::min<size_t>(n, ids.size()));
+        Value t = Value::array();
+        for (uint32_t x : ids) t.push(Value::num(x));
+        named.push(t);
+        c.term_ids.push_back(ids);
+    }
+    for (uint64_t v : r.identities.value) val.push(str(v));
+    for (uint64_t v : r.identities.alpha) al.push(str(v));
+    id.set("rows", rows);
+    id.set("value", val);
+    id.set("alpha", al);
+    if (c.named) id.set("failing_terms", named);
+    j.set("identities", id);
+    printf("%s", zkgpu_host::audit_format(r, c).c_str());
+    mkdir(dir.c_str(), 0775);
+    write_json(dir + "/trace_audit.json", j);
+    return r.clean ? 0 : 3;
+}
 
 // The RCCL id through a file: rank 0 writes it (atomic rename), the others
 // poll.  Every file carries this run's tag -- ZKGPU_RUN_ID if set, else the
@@ -266,6 +373,7 @@ static int prove(const std::string &config_path, const Shard &sh)
     if (sh.check_trace && zkgpu_stark_check_names_set(h, 1))
         fprintf(stderr, "--check-trace: %s; the failing rows will be named, not the identities\n",
                 zkgpu_stark_last_error());
+    if (sh.audit) return audit_trace(h, si, info, key("outputPath"));
     const auto t1 = clk::now();
     const uint64_t len = zkgpu_stark_proof_len(h);
     if (len != flat_len(info)) throw std::runtime_error("proof length mismatch");
@@ -318,6 +426,11 @@ int main(int argc, char **argv)
                 a += 1;
                 continue;
             }
+            if (opt == "--audit") {
+                sh.audit = true;
+                a += 1;
+                continue;
+            }
             if (opt == "--shard") {
                 unsigned r = 0, w = 0;
                 if (sscanf(argv[a + 1], "%u/%u", &r, &w) != 2 || !w || r >= w)
@@ -339,9 +452,13 @@ int main(int argc, char **argv)
             throw std::runtime_error("--stream-trace is for the single-GPU prover (no --comm)");
         if (sh.check_trace && sh.world > 1)
             throw std::runtime_error("--check-trace is for the single-GPU prover (not with --shard at WORLD > 1)");
+        if (sh.audit && (sh.world > 1 || !sh.comm.empty()))
+            throw std::runtime_error("--audit is for the single-GPU prover (not with --shard at WORLD > 1 or --comm)");
+        if (sh.audit && (sh.stream_trace || sh.check_trace))
+            throw std::runtime_error("--audit runs no proof: not with --stream-trace or --check-trace");
         if (argc == a + 1 && argv[a][0] != '-') return prove(argv[a], sh);
         fprintf(stderr,
-                "usage: %s [--stream-trace] [--check-trace] [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] "
+                "usage: %s [--stream-trace] [--check-trace] [--audit] [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] "
                 "<config.json>\n"
                 "       %s --info <starkinfo.json>\n"
                 "       %s --zkin <starkinfo.json> <flat proof> <publics.json> <outdir>\n",

@@ -738,6 +738,15 @@ public:
     {
         return fail("stark (sharded): z_diag: single-GPU provers only (a rank holds a row block of num and den)");
     }
+    int audit(uint32_t, zkgpu_audit_report *) override
+    {
+        return fail("stark (sharded): audit: single-GPU provers only (a rank holds a row block of the n-domain "
+                    "sections)");
+    }
+    int audit_format(char *, uint64_t) const override
+    {
+        return fail("stark (sharded): audit_format: single-GPU provers only");
+    }
     int check_names_set(int) override
     {
         return fail("stark (sharded): check_names_set is single-GPU only (as check_set)");

@@ -23,6 +23,7 @@
 
 #include "../../include/zkgpu.h"
 #include "../../include/zkgpu_stark.h"
+#include "zkgpu_audit_format.hpp"
 
 namespace zkgpu_host {
 
@@ -215,6 +216,8 @@ public:
     int stream_register = 0;
     uint64_t *stream_stage = nullptr;
     bool cm1_broken = false;
+    // a whole trace has been loaded (set_cm1 / witness / a streamed or background load): the audit's precondition
+    bool cm1_loaded = false;
 
     virtual ~Starks()
     {
@@ -650,6 +653,7 @@ public:
         if (run(step1, false, ch, ev0, 0)) return -1;
         CK(zkgpu_synchronize());
         cm1_consumed = cm1_broken = false;
+        cm1_loaded = true;
         return 0;
     }
 
@@ -661,6 +665,7 @@ public:
         if (zkgpu_load_rows_dev(S.sec[SEC_CM1_N], N, rows, N, info.n_cm1, 0, 0))
             return fail("set_cm1: %s", zkgpu_last_error());
         cm1_consumed = cm1_broken = false;
+        cm1_loaded = true;
         return 0;
     }
 
@@ -723,7 +728,10 @@ public:
             rc = rc ? rc : r;
         }
         if (rc) return fail("set_cm1_async: %s", zkgpu_last_error());
-        if (use) std::swap(S.sec[SEC_CM1_N], cm1_next);
+        if (use) {
+            std::swap(S.sec[SEC_CM1_N], cm1_next);
+            cm1_loaded = true;
+        }
         return 0;
     }
 
@@ -928,6 +936,7 @@ public:
         }
         if (rc_close) return fail("prove_from_rows: %s", zkgpu_last_error());
         cm1_broken = false;
+        cm1_loaded = true;
         return tstop("STARK_STEP_1_STREAM");
     }
 
@@ -1196,12 +1205,24 @@ public:
             check_mode = ZKGPU_CHECK_OFF;
             return 0;
         }
+        std::string why;
+        if (!check_prepare(why)) {
+            check_mode = ZKGPU_CHECK_OFF;
+            return fail("check_set: %s; the check is off", why.c_str());
+        }
+        check_mode = mode;
+        return 0;
+    }
+    // the n-domain rewrite of step42ns (once) and the check's device block; false: `why` says what
+    // was refused (the mode is the caller's business: the audit uses the check without setting one)
+    bool check_prepare(std::string &why)
+    {
         if (check_opnd.empty()) {
             std::vector<zxp_operand> o(step42ns.opnd.size() + 1);
             if (zkgpu_zxp_to_n_domain(o.data(), step42ns.instr.data(), (uint32_t)step42ns.instr.size(),
                                       step42ns.opnd.data(), (uint32_t)step42ns.opnd.size(), eb)) {
-                check_mode = ZKGPU_CHECK_OFF;
-                return fail("check_set: step42ns: %s; the check is off", zkgpu_last_error());
+                why = std::string("step42ns: ") + zkgpu_last_error();
+                return false;
             }
             o.resize(step42ns.opnd.size());
             check_opnd.swap(o);
@@ -1209,13 +1230,12 @@ public:
         if (!check_dev) {
             void *v = nullptr;
             if (zkgpu_dev_malloc(&v, (4 + ZKGPU_CHECK_MAX_ROWS) * 8)) {
-                check_mode = ZKGPU_CHECK_OFF;
-                return fail("check_set: %s; the check is off", zkgpu_last_error());
+                why = zkgpu_last_error();
+                return false;
             }
             check_dev = (uint64_t *)v;
         }
-        check_mode = mode;
-        return 0;
+        return true;
     }
 
     // between the last stage-3 program and stage 3's commit: every n-domain
@@ -1224,6 +1244,32 @@ public:
     // takes its own: the getField of a COPY of the transcript as it stands
     // (challenges 2 and 3 drawn); the proof's transcript is not touched.
     int check_run(const Transcript &tr, const uint64_t ch[24])
+    {
+        if (check_queue(tr, ch, "ZKGPU_CHECK_CONSTRAINTS")) return -1;
+        if (check_mode == ZKGPU_CHECK_REPORT) {
+            check_pending = true;
+            return 0;
+        }
+        if (check_readback()) return -1;  // STOP: the one synchronisation
+        if (check_res.n_bad) {
+            // the terms that fail at the first row, up to 8 (with naming on)
+            std::string tail;
+            if (names_on) {
+                const std::vector<uint32_t> &ids = names_ids[0];
+                if (!ids.empty()) tail = "; failing terms there:";
+                for (size_t k = 0; k < ids.size() && k < 8; k++) tail += " " + std::to_string(ids[k]);
+                if (ids.size() > 8) tail += " and " + std::to_string(ids.size() - 8) + " more";
+                if (!ids.empty()) tail += " (zkgpu_stark_check_named)";
+            }
+            return fail("constraint check: %llu of the 2^%u = %llu rows of the trace break the AIR; the first is row "
+                        "%llu (zkgpu_stark_check_result lists the lowest %u)%s",
+                        (unsigned long long)check_res.n_bad, info.n_bits, (unsigned long long)N,
+                        (unsigned long long)check_res.rows[0], (unsigned)ZKGPU_CHECK_MAX_ROWS, tail.c_str());
+        }
+        return 0;
+    }
+    // the check's launches (and, with naming on, the names') under one timer line; nothing is read back
+    int check_queue(const Transcript &tr, const uint64_t ch[24], const char *timer)
     {
         tstart();
         Transcript fork = tr;
@@ -1261,28 +1307,7 @@ public:
                                        (uint32_t)publics.size(), ev0, 0, nullptr, nullptr, 0, 1, check_dev + 1,
                                        ZKGPU_CHECK_MAX_ROWS));
         }
-        if (tstop("ZKGPU_CHECK_CONSTRAINTS")) return -1;
-        if (check_mode == ZKGPU_CHECK_REPORT) {
-            check_pending = true;
-            return 0;
-        }
-        if (check_readback()) return -1;  // STOP: the one synchronisation
-        if (check_res.n_bad) {
-            // the terms that fail at the first row, up to 8 (with naming on)
-            std::string tail;
-            if (names_on) {
-                const std::vector<uint32_t> &ids = names_ids[0];
-                if (!ids.empty()) tail = "; failing terms there:";
-                for (size_t k = 0; k < ids.size() && k < 8; k++) tail += " " + std::to_string(ids[k]);
-                if (ids.size() > 8) tail += " and " + std::to_string(ids.size() - 8) + " more";
-                if (!ids.empty()) tail += " (zkgpu_stark_check_named)";
-            }
-            return fail("constraint check: %llu of the 2^%u = %llu rows of the trace break the AIR; the first is row "
-                        "%llu (zkgpu_stark_check_result lists the lowest %u)%s",
-                        (unsigned long long)check_res.n_bad, info.n_bits, (unsigned long long)N,
-                        (unsigned long long)check_res.rows[0], (unsigned)ZKGPU_CHECK_MAX_ROWS, tail.c_str());
-        }
-        return 0;
+        return tstop(timer);
     }
     int check_readback()
     {
@@ -1333,12 +1358,24 @@ public:
             names_on = false;
             return 0;
         }
+        std::string why;
+        if (!names_prepare(why)) {
+            names_on = false;
+            return fail("check_names_set: %s; naming is off", why.c_str());
+        }
+        names_on = true;
+        return 0;
+    }
+    // the split of the n-domain step42ns (once) and the names' device block; false: `why` says
+    // what was refused (whether naming is on is the caller's business, as with check_prepare)
+    bool names_prepare(std::string &why)
+    {
         if (names_terms.empty()) {
             std::vector<zxp_operand> nd(step42ns.opnd.size() + 1);
             if (zkgpu_zxp_to_n_domain(nd.data(), step42ns.instr.data(), (uint32_t)step42ns.instr.size(),
                                       step42ns.opnd.data(), (uint32_t)step42ns.opnd.size(), eb)) {
-                names_on = false;
-                return fail("check_names_set: step42ns: %s; naming is off", zkgpu_last_error());
+                why = std::string("step42ns: ") + zkgpu_last_error();
+                return false;
             }
             const size_t ni = step42ns.instr.size(), no = step42ns.opnd.size();
             std::vector<zxp_instr> ti(2 * ni + 1);
@@ -1347,8 +1384,8 @@ public:
             uint32_t n_i = 0, n_o = 0, n_t = 0;
             if (zkgpu_zxp_split_constraints(ti.data(), &n_i, to.data(), &n_o, tt.data(), &n_t, step42ns.instr.data(),
                                             (uint32_t)ni, nd.data(), (uint32_t)no, 4)) {
-                names_on = false;
-                return fail("check_names_set: step42ns: %s; naming is off", zkgpu_last_error());
+                why = std::string("step42ns: ") + zkgpu_last_error();
+                return false;
             }
             ti.resize(n_i), to.resize(n_o), tt.resize(n_t);
             names_instr.swap(ti), names_opnd.swap(to), names_terms.swap(tt);
@@ -1356,13 +1393,12 @@ public:
         if (!names_dev) {
             void *v = nullptr;
             if (zkgpu_dev_malloc(&v, 3 * names_terms.size() * ZKGPU_CHECK_MAX_ROWS * 8)) {
-                names_on = false;
-                return fail("check_names_set: %s; naming is off", zkgpu_last_error());
+                why = zkgpu_last_error();
+                return false;
             }
             names_dev = (uint64_t *)v;
         }
-        names_on = true;
-        return 0;
+        return true;
     }
     int check_terms(zxp_split_term *out, uint32_t max, uint32_t *n) const
     {
@@ -1601,12 +1637,17 @@ public:
     }
 
     // calculateZ of every grand product (starks.cpp:165-189), n domain
-    virtual int z_all()
+    std::vector<zkgpu_z_req> z_requests() const
     {
         std::vector<zkgpu_z_req> req(info.n_zctx);
         for (uint32_t z = 0; z < info.n_zctx; z++)
             req[z] = {S.sec[SEC_CM3_N] + (uint64_t)zctx[3 * z + 2] * N, N, S.sec[SEC_TMP_N] + (uint64_t)zctx[3 * z] * N, N,
                       S.sec[SEC_TMP_N] + (uint64_t)zctx[3 * z + 1] * N, N};
+        return req;
+    }
+    virtual int z_all()
+    {
+        const std::vector<zkgpu_z_req> req = z_requests();
         std::vector<int> closes(info.n_zctx + 1, 0);
         CK(zkgpu_calculate_z_many_dev(req.data(), info.n_zctx, N, closes.data()));
         uint32_t n_open = 0, first = 0;
@@ -1631,26 +1672,11 @@ public:
         zdiag = zkgpu_z_diag{};
         zdiag.z = z;
         zdiag.n_open = n_open;
-        constexpr uint32_t M = ZKGPU_Z_DIAG_MAX, BLK = 1 + 3 * M;
-        uint64_t h[2 * BLK];
-        void *dev = nullptr;
-        int rc = zkgpu_dev_malloc(&dev, sizeof h);
-        if (!rc)
-            rc = zkgpu_multiset_diff_dev((uint64_t *)dev, S.sec[SEC_TMP_N] + (uint64_t)zctx[3 * z] * N, N,
-                                         S.sec[SEC_TMP_N] + (uint64_t)zctx[3 * z + 1] * N, N, N, 3, M);
-        if (!rc) rc = zkgpu_memcpy_d2h(h, dev, sizeof h);
-        const std::string why = rc ? zkgpu_last_error() : "";
-        (void)zkgpu_dev_free(dev);
-        if (rc)
+        std::string why;
+        if (!z_compare(z, zdiag.n_num, zdiag.n_den, zdiag.num, zdiag.den, why))
             return fail("calculateZ: grand product %u does not close (%u of %u do not); the comparison of its num and "
                         "den columns was skipped: %s", z, n_open, info.n_zctx, why.c_str());
         zdiag.ran = 1;
-        zdiag.n_num = h[0];
-        zdiag.n_den = h[BLK];
-        for (uint32_t k = 0; k < M; k++) {
-            zdiag.num[k] = {h[1 + 3 * k], h[2 + 3 * k], h[3 + 3 * k]};
-            zdiag.den[k] = {h[BLK + 1 + 3 * k], h[BLK + 2 + 3 * k], h[BLK + 3 + 3 * k]};
-        }
         char side[2][160];
         for (int b = 0; b < 2; b++) {
             const uint64_t cnt = b ? zdiag.n_den : zdiag.n_num;
@@ -1667,11 +1693,219 @@ public:
                     side[0], side[1]);
     }
 
+    // the num and den columns of product z compared as multisets into the lists of zkgpu_z_diag (the
+    // audit's too); false: the scratch or the result block could not be had, `why` says which
+    bool z_compare(uint32_t z, uint64_t &n_num, uint64_t &n_den, zkgpu_z_diag_val *num, zkgpu_z_diag_val *den,
+                   std::string &why)
+    {
+        constexpr uint32_t M = ZKGPU_Z_DIAG_MAX, BLK = 1 + 3 * M;
+        uint64_t h[2 * BLK];
+        void *dev = nullptr;
+        int rc = zkgpu_dev_malloc(&dev, sizeof h);
+        if (!rc)
+            rc = zkgpu_multiset_diff_dev((uint64_t *)dev, S.sec[SEC_TMP_N] + (uint64_t)zctx[3 * z] * N, N,
+                                         S.sec[SEC_TMP_N] + (uint64_t)zctx[3 * z + 1] * N, N, N, 3, M);
+        if (!rc) rc = zkgpu_memcpy_d2h(h, dev, sizeof h);
+        why = rc ? zkgpu_last_error() : "";
+        (void)zkgpu_dev_free(dev);
+        if (rc) return false;
+        n_num = h[0];
+        n_den = h[BLK];
+        for (uint32_t k = 0; k < M; k++) {
+            num[k] = {h[1 + 3 * k], h[2 + 3 * k], h[3 + 3 * k]};
+            den[k] = {h[BLK + 1 + 3 * k], h[BLK + 2 + 3 * k], h[BLK + 3 + 3 * k]};
+        }
+        return true;
+    }
+
     virtual int z_diag(zkgpu_z_diag *out) const
     {
         if (!out) return fail("z_diag: null buffer");
         *out = zdiag;
         return 0;
+    }
+
+    // ---- trace audit (include/zkgpu_stark.h zkgpu_stark_audit): the stage-2
+    // and stage-3 work of prove_body on the n domain, run to the end whatever
+    // it finds, with challenges from a transcript that holds no root.  It
+    // writes tmpExp_n, cm2_n, cm3_n and the head of q -- every one dead between
+    // proofs under both plans -- and reads cm1_n, which it leaves as it is.
+    // The programs go through run(), not run_prog(): no probe record is taken.
+    zkgpu_audit_report audit_rep = {};
+    bool audit_valid = false, audit_named = false;
+    std::string audit_why;  // why the identities did not run although no plookup missed
+    std::vector<std::vector<uint32_t>> audit_terms;  // with naming: the failing term ids per listed row
+
+    // layer A's finding: the f values of plookup k that its table does not hold (a 34-word result
+    // block that lives for this call, as z_compare's)
+    int audit_misses(uint32_t k, zkgpu_audit_pu &e)
+    {
+        constexpr uint32_t M = ZKGPU_LOOKUP_MISS_MAX;
+        const uint32_t *q = &pu[5 * k];
+        uint64_t h[2 + 2 * M];
+        void *dev = nullptr;
+        int rc = zkgpu_dev_malloc(&dev, sizeof h);
+        if (!rc)
+            rc = zkgpu_lookup_misses_dev((uint64_t *)dev, S.sec[SEC_TMP_N] + (uint64_t)q[0] * N, N,
+                                         S.sec[SEC_TMP_N] + (uint64_t)q[1] * N, N, N, q[4], M);
+        if (!rc) rc = zkgpu_memcpy_d2h(h, dev, sizeof h);
+        const std::string why = rc ? zkgpu_last_error() : "";
+        (void)zkgpu_dev_free(dev);
+        if (rc) return fail("audit: plookup %u: %s", k, why.c_str());
+        e.pu = k;
+        e.n_rows = h[0];
+        e.n_vals = h[1];
+        for (uint32_t j = 0; j < M; j++) e.vals[j] = {h[2 + 2 * j], h[3 + 2 * j]};
+        return 0;
+    }
+
+    virtual int audit(uint32_t flags, zkgpu_audit_report *out)
+    {
+        if (!out) return fail("audit: null buffer");
+        if (flags & ~ZKGPU_AUDIT_NAMES) return fail("audit: unknown flags 0x%x", flags);
+        if (cm1_broken)
+            return fail("audit: the last streamed load (prove_from_rows) failed part-way: no whole trace is loaded; "
+                        "load one with set_cm1 or witness first");
+        if (lean() && cm1_consumed)
+            return fail("audit: the previous proof consumed the trace (lean memory plan: cm1_n is extended in place); "
+                        "load the next one with set_cm1 or witness first");
+        if (!cm1_loaded) return fail("audit: no trace is loaded; load one with set_cm1 or witness first");
+        audit_valid = false;
+        audit_rep = zkgpu_audit_report{};
+        audit_why.clear();
+        check_pending = false;
+        check_res = zkgpu_check_result{};
+        for (uint64_t &row : check_res.rows) row = UINT64_MAX;  // an empty list, should layer C not run
+        zdiag = zkgpu_z_diag{};
+        names_ran = false;
+        for (auto &v : names_ids) v.clear();
+        for (auto &v : names_vals) v.clear();
+        timers.clear();
+        pend_t.clear();
+        pend_x.clear();
+        n_marks = 0;
+        const auto tall = clk::now();
+        zkgpu_audit_report &R = audit_rep;
+        // the audit's own challenges: verkey and publics, no root
+        Transcript tr;
+        tr.put(verkey, 4);
+        tr.put(publics.data(), publics.size());
+        uint64_t ch[24] = {0};
+        for (int k = 0; k < 4; k++) tr.get_field(ch + 3 * k);
+        {
+            Transcript fork = tr;  // (check_queue draws the same value from its own copy)
+            uint64_t alpha[3];
+            fork.get_field(alpha);
+            if (fork.err) return fail("audit: transcript hashing failed: %s", zkgpu_last_error());
+            memcpy(R.challenges, ch, 12 * 8);
+            memcpy(R.challenges + 12, alpha, 24);
+            memcpy(check_res.alpha, alpha, 24);  // (reported whether or not layer C runs)
+        }
+        const uint64_t ev0[3] = {0, 0, 0};
+        // as a proof after stage 1: the columns no stage writes read 0
+        if (lean() && (zero_unwritten(SEC_TMP_N) || zero_unwritten(SEC_CM2_N) || zero_unwritten(SEC_CM3_N)))
+            return -1;
+        // ---- layer A: every plookup
+        tstart();
+        if (run(step2, false, ch, ev0, 0)) return -1;
+        if (tstop("AUDIT_STEP2")) return -1;
+        if (info.n_pu) {
+            tstart();
+            for (uint32_t k = 0; k < info.n_pu; k++) {
+                const uint32_t *q = &pu[5 * k];
+                uint64_t *h1 = S.sec[SEC_CM2_N] + (uint64_t)q[2] * N, *h2 = S.sec[SEC_CM2_N] + (uint64_t)q[3] * N;
+                const uint64_t *f = S.sec[SEC_TMP_N] + (uint64_t)q[0] * N, *t = S.sec[SEC_TMP_N] + (uint64_t)q[1] * N;
+                uint64_t miss = ~0ULL;
+                const int rc = zkgpu_h1h2_dev(h1, N, h2, N, f, N, t, N, N, q[4], &miss);
+                if (!rc) continue;
+                if (miss == ~0ULL) return fail("audit: calculateH1H2: %s", zkgpu_last_error());
+                // a miss: h1 / h2 were not written; they read zero from here on
+                CK(zkgpu_memset_dev(h1, 0, (uint64_t)q[4] * N * 8));
+                CK(zkgpu_memset_dev(h2, 0, (uint64_t)q[4] * N * 8));
+                if (R.n_pu_bad++ < ZKGPU_AUDIT_MAX_PU && audit_misses(k, R.pu[R.n_pu_bad - 1])) return -1;
+            }
+            if (tstop("AUDIT_H1H2")) return -1;
+        }
+        // ---- layer B: every grand product
+        tstart();
+        if (run(step3prev, false, ch, ev0, 0)) return -1;
+        if (tstop("AUDIT_STEP3PREV")) return -1;
+        tstart();
+        {
+            const std::vector<zkgpu_z_req> req = z_requests();
+            std::vector<int> closes(info.n_zctx + 1, 0);
+            // (every z column is written, closed or not: layer C reads them)
+            CK(zkgpu_calculate_z_many_dev(req.data(), info.n_zctx, N, closes.data()));
+            for (uint32_t z = 0; z < info.n_zctx; z++) {
+                if (closes[z]) continue;
+                if (R.n_z_open++ >= ZKGPU_AUDIT_MAX_Z) continue;
+                zkgpu_audit_z &e = R.z[R.n_z_open - 1];
+                e.z = z;
+                // the products one after the other through the shared workspace; without the scratch
+                // the product is still listed
+                std::string why;
+                e.compared = z_compare(z, e.n_num, e.n_den, e.num, e.den, why);
+            }
+        }
+        if (tstop("AUDIT_Z")) return -1;
+        if (R.n_z_open) {  // zkgpu_stark_z_diag: the lowest open product
+            const zkgpu_audit_z &e = R.z[0];
+            zdiag.ran = e.compared;
+            zdiag.z = e.z;
+            zdiag.n_open = R.n_z_open;
+            zdiag.n_num = e.n_num;
+            zdiag.n_den = e.n_den;
+            memcpy(zdiag.num, e.num, sizeof zdiag.num);
+            memcpy(zdiag.den, e.den, sizeof zdiag.den);
+        }
+        // ---- layer C: the identities, unless a plookup missed (its h1 / h2 read zero)
+        audit_named = false;
+        audit_terms.clear();
+        if (!R.n_pu_bad) {
+            if (!step3.instr.empty()) {
+                tstart();
+                if (run(step3, false, ch, ev0, 0)) return -1;
+                if (tstop("AUDIT_STEP3")) return -1;
+            }
+            if (check_prepare(audit_why)) {
+                std::string why_names;
+                const bool was_on = names_on;
+                names_on = (flags & ZKGPU_AUDIT_NAMES) && names_prepare(why_names);  // refused: rows only
+                const int rc = check_queue(tr, ch, "AUDIT_CONSTRAINTS") || check_readback();
+                audit_named = names_on;
+                if (audit_named) audit_terms.assign(names_ids, names_ids + ZKGPU_CHECK_MAX_ROWS);
+                names_on = was_on;
+                if (rc) return -1;
+            }
+        }
+        R.identities = check_res;
+        R.clean = !R.n_pu_bad && !R.n_z_open && check_res.ran && !check_res.n_bad;
+        if (flush_timers()) return -1;
+        if (tr.err) return fail("audit: transcript hashing failed: %s", zkgpu_last_error());
+        timers.emplace_back("AUDIT_TOTAL", std::chrono::duration<double, std::milli>(clk::now() - tall).count());
+        audit_valid = true;
+        *out = R;
+        return 0;
+    }
+
+    virtual int audit_format(char *buf, uint64_t len) const
+    {
+        if (!audit_valid) return fail("audit_format: no audit has run on this prover");
+        if (len && !buf) return fail("audit_format: null buffer");
+        AuditContext c;
+        c.n_bits = info.n_bits;
+        c.n_pu = info.n_pu;
+        c.n_zctx = info.n_zctx;
+        c.identities_why = audit_why;
+        c.named = audit_named;
+        c.term_ids = audit_terms;
+        const std::string s = zkgpu_host::audit_format(audit_rep, c);
+        if (len) {
+            const size_t n = std::min<size_t>(s.size(), len - 1);
+            memcpy(buf, s.data(), n);
+            buf[n] = 0;
+        }
+        return (int)s.size();
     }
 
     // LEv / LpEv: the n-domain Lagrange weights of xi and w xi (see prove),
@@ -1972,6 +2206,8 @@ int zkgpu_stark_probe_set(void *h, const uint64_t *rows_n, uint32_t n_rows_n, co
 int zkgpu_stark_check_set(void *h, uint32_t mode) { return ((Starks *)h)->check_set(mode); }
 int zkgpu_stark_check_result(void *h, zkgpu_check_result *out) { return ((Starks *)h)->check_result(out); }
 int zkgpu_stark_z_diag(void *h, zkgpu_z_diag *out) { return ((Starks *)h)->z_diag(out); }
+int zkgpu_stark_audit(void *h, uint32_t flags, zkgpu_audit_report *out) { return ((Starks *)h)->audit(flags, out); }
+int zkgpu_stark_audit_format(void *h, char *buf, uint64_t len) { return ((Starks *)h)->audit_format(buf, len); }
 int zkgpu_stark_check_names_set(void *h, int on) { return ((Starks *)h)->check_names_set(on); }
 int zkgpu_stark_check_terms(void *h, zxp_split_term *out, uint32_t max, uint32_t *n)
 {

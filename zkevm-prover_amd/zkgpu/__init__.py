@@ -117,6 +117,8 @@ _SIGS = {
     "zkgpu_h1h2_dev": (ctypes.c_int, [vp, u64, vp, u64, vp, u64, vp, u64, u64, u32, pu64]),
     "zkgpu_multiset_diff_workspace_bytes": (u64, [u64]),
     "zkgpu_multiset_diff_dev": (ctypes.c_int, [vp, vp, u64, vp, u64, u64, u32, u32]),
+    "zkgpu_lookup_misses_workspace_bytes": (u64, [u64]),
+    "zkgpu_lookup_misses_dev": (ctypes.c_int, [vp, vp, u64, vp, u64, u64, u32, u32]),
     "zkgpu_h1h2_shard_route": (ctypes.c_int, [vp, u64, vp, vp, vp, u64, vp, u64, u64, u64, u32, u32]),
     "zkgpu_h1h2_shard_owner": (ctypes.c_int, [vp, vp, u64, u32, pu64]),
     "zkgpu_h1h2_shard_counts": (ctypes.c_int, [vp, vp, pu64, vp, vp, u64, u64, u64]),
@@ -865,6 +867,37 @@ def multiset_diff_dev(out, a, a_ld, b, b_ld, n, dim, max_vals):
     past the last (zkgpu_multiset_diff_dev; queued on the library stream)"""
     _check(lib().zkgpu_multiset_diff_dev(_addr(out), _addr(a), a_ld, _addr(b), b_ld, n, dim, max_vals),
            "zkgpu_multiset_diff_dev")
+
+
+def lookup_misses_workspace_bytes(n):
+    """device scratch bytes of lookup_misses_dev at n rows (no GPU needed)"""
+    return int(lib().zkgpu_lookup_misses_workspace_bytes(n))
+
+
+def lookup_misses_dev(out, f, f_ld, t, t_ld, n, dim, max_vals):
+    """out (device, 2 + 2 * max_vals words): the rows of the n-row column f
+    (dim 1 or 3, column-major) whose value no row of t holds, the distinct
+    such values, then max_vals pairs {the value's first row in f, its count
+    in f} by ascending row, (2^64 - 1, 0) past the last
+    (zkgpu_lookup_misses_dev; queued on the library stream)"""
+    _check(lib().zkgpu_lookup_misses_dev(_addr(out), _addr(f), f_ld, _addr(t), t_ld, n, dim, max_vals),
+           "zkgpu_lookup_misses_dev")
+
+
+def lookup_misses(f, t, max_vals=16):
+    """host columns f, t ((dim, n) or (n,) uint64) -> (n_rows, n_vals,
+    [(first row in f, count in f)]): lookup_misses_dev through device copies"""
+    f, t = (np.ascontiguousarray(np.atleast_2d(np.asarray(c, dtype=np.uint64))) for c in (f, t))
+    if f.shape != t.shape or f.ndim != 2:
+        raise ValueError("f and t must have the same shape, (dim, n) or (n,)")
+    dim, n = f.shape
+    d_f, d_t = to_device(f.ravel() if n else np.zeros(1, np.uint64)), to_device(t.ravel() if n else np.zeros(1, np.uint64))
+    d_out = to_device(np.zeros(2 + 2 * max_vals, np.uint64))
+    lookup_misses_dev(d_out, d_f, n, d_t, n, n, dim, max_vals)
+    synchronize()
+    w = from_device(d_out)
+    pairs = [(int(w[2 + 2 * k]), int(w[3 + 2 * k])) for k in range(max_vals) if int(w[2 + 2 * k]) != 2**64 - 1]
+    return int(w[0]), int(w[1]), pairs
 
 
 # calculateH1H2 over row-sharded f / t (include/zkgpu.h zkgpu_h1h2_shard_*;

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from . import ZkgpuError, lib as _zk_lib
+from . import ZkgpuError, _absent, lib as _zk_lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 STARK_LIB = os.path.join(os.environ.get("ZKGPU_LIB_DIR") or os.path.join(os.path.dirname(_HERE), "lib"),
@@ -80,6 +80,35 @@ class ZDiag(ctypes.Structure):
                 ("den", ZDiagVal * Z_DIAG_MAX)]
 
 
+# trace audit (include/zkgpu_stark.h ZKGPU_AUDIT_*)
+AUDIT_NAMES = 1
+AUDIT_MAX_PU, AUDIT_MAX_Z, LOOKUP_MISS_MAX = 8, 8, 16
+
+
+class LookupMiss(ctypes.Structure):
+    """zkgpu_lookup_miss (include/zkgpu_stark.h)"""
+    _fields_ = [("row", ctypes.c_uint64), ("count", ctypes.c_uint64)]
+
+
+class AuditPu(ctypes.Structure):
+    """zkgpu_audit_pu (include/zkgpu_stark.h)"""
+    _fields_ = [("pu", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_vals", ctypes.c_uint64),
+                ("vals", LookupMiss * LOOKUP_MISS_MAX)]
+
+
+class AuditZ(ctypes.Structure):
+    """zkgpu_audit_z (include/zkgpu_stark.h)"""
+    _fields_ = [("z", ctypes.c_uint32), ("compared", ctypes.c_uint32), ("n_num", ctypes.c_uint64),
+                ("n_den", ctypes.c_uint64), ("num", ZDiagVal * Z_DIAG_MAX), ("den", ZDiagVal * Z_DIAG_MAX)]
+
+
+class AuditReport(ctypes.Structure):
+    """zkgpu_audit_report (include/zkgpu_stark.h)"""
+    _fields_ = [("clean", ctypes.c_uint32), ("challenges", ctypes.c_uint64 * 15), ("n_pu_bad", ctypes.c_uint32),
+                ("pu", AuditPu * AUDIT_MAX_PU), ("n_z_open", ctypes.c_uint32), ("z", AuditZ * AUDIT_MAX_Z),
+                ("identities", CheckResult)]
+
+
 _slib = None
 
 
@@ -113,6 +142,8 @@ def slib():
             ("zkgpu_stark_check_set", ctypes.c_int, [vp, ctypes.c_uint32]),
             ("zkgpu_stark_check_result", ctypes.c_int, [vp, ctypes.POINTER(CheckResult)]),
             ("zkgpu_stark_z_diag", ctypes.c_int, [vp, ctypes.POINTER(ZDiag)]),
+            ("zkgpu_stark_audit", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.POINTER(AuditReport)]),
+            ("zkgpu_stark_audit_format", ctypes.c_int, [vp, ctypes.c_char_p, u64]),
             ("zkgpu_stark_check_names_set", ctypes.c_int, [vp, ctypes.c_int]),
             ("zkgpu_stark_check_terms", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp]),
             ("zkgpu_stark_check_named", ctypes.c_int, [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp]),
@@ -135,7 +166,10 @@ def slib():
             ("zkgpu_transcript_get_field", ctypes.c_int, [vp, vp]),
             ("zkgpu_transcript_get_permutations", ctypes.c_int, [vp, vp, u64, u64]),
         ]:
-            f = getattr(L, name)
+            f = getattr(L, name, None)
+            if f is None:  # an older build (A/B runs, ZKGPU_LIB_DIR): the entry point fails when called
+                setattr(L, name, _absent(name))
+                continue
             f.restype = res
             f.argtypes = args
         _slib = L
@@ -496,6 +530,44 @@ class GpuStark:
 
         return {"ran": int(r.ran), "z": int(r.z), "n_open": int(r.n_open), "n_num": int(r.n_num),
                 "n_den": int(r.n_den), "num": vals(r.num), "den": vals(r.den)}
+
+    def audit(self, names=False):
+        """every broken plookup, grand product and identity of the loaded
+        trace, without proving (zkgpu_stark_audit): dict with the keys of
+        zkgpu_audit_report -- clean, challenges (15 ints), n_pu_bad, pu (the
+        lowest failing plookups: dict(pu, n_rows, n_vals, vals [(first row in
+        f, rows in f)])), n_z_open, z (the lowest open products: dict(z,
+        compared, n_num, n_den, num, den) as z_diag), identities (as
+        check_result; ran = 0 when a plookup missed).  names: also the terms
+        at the failing rows (check_named afterwards).  Not a verifier: the
+        challenges do not depend on the trace."""
+        r = AuditReport()
+        _check(slib().zkgpu_stark_audit(self.h, AUDIT_NAMES if names else 0, ctypes.byref(r)), "zkgpu_stark_audit")
+
+        def zvals(a):
+            return [(int(v.row), int(v.count_num), int(v.count_den)) for v in a if v.row != 2**64 - 1]
+
+        i = r.identities
+        return {
+            "clean": int(r.clean), "challenges": [int(x) for x in r.challenges], "n_pu_bad": int(r.n_pu_bad),
+            "pu": [{"pu": int(e.pu), "n_rows": int(e.n_rows), "n_vals": int(e.n_vals),
+                    "vals": [(int(v.row), int(v.count)) for v in e.vals if v.row != 2**64 - 1]}
+                   for e in r.pu[:min(r.n_pu_bad, AUDIT_MAX_PU)]],
+            "n_z_open": int(r.n_z_open),
+            "z": [{"z": int(e.z), "compared": int(e.compared), "n_num": int(e.n_num), "n_den": int(e.n_den),
+                   "num": zvals(e.num), "den": zvals(e.den)} for e in r.z[:min(r.n_z_open, AUDIT_MAX_Z)]],
+            "identities": {"ran": int(i.ran), "n_bad": int(i.n_bad),
+                           "rows": [int(x) for x in i.rows if x != 2**64 - 1], "value": [int(x) for x in i.value],
+                           "alpha": [int(x) for x in i.alpha]},
+        }
+
+    def audit_text(self):
+        """the last audit's report as text, one finding per line (zkgpu_stark_audit_format)"""
+        buf = ctypes.create_string_buffer(1 << 16)
+        n = slib().zkgpu_stark_audit_format(self.h, buf, len(buf))
+        if n < 0:
+            _check(n, "zkgpu_stark_audit_format")
+        return buf.value.decode()
 
     def check_names_set(self, on=True):
         """naming of every later checked proof (zkgpu_stark_check_names_set):
