@@ -6,34 +6,9 @@ bit-exact, dims 1 and 3, heavy duplicates, the missing-value error."""
 import numpy as np
 import pytest
 
+from h1h2_cases import reference_rows as py_h1h2  # polinomial.hpp:349-463 step by step
+
 P = 0xFFFFFFFF00000001
-
-
-def py_h1h2(f, t):
-    """polinomial.hpp:349-463 step by step (small n only)."""
-    n = len(t)
-    key = (lambda r: tuple(int(v) % P for v in np.atleast_1d(r)))
-    last = {}
-    for i in range(n):
-        last[key(t[i])] = i  # the chain entry keeps the latest index (:380-383)
-    counter = [1] * n
-    for i in range(n):
-        k = key(f[i])
-        if k not in last:
-            raise ValueError("Number not included: w=%d" % i)
-        counter[last[k]] += 1
-    h1, h2 = np.zeros_like(t), np.zeros_like(t)
-    idx = 0
-    for i in range(n):
-        if counter[idx] == 0:
-            idx += 1
-        counter[idx] -= 1
-        h1[i] = t[idx]
-        if counter[idx] == 0:
-            idx += 1
-        counter[idx] -= 1
-        h2[i] = t[idx]
-    return h1, h2
 
 
 def lookup_case(rng, n, dim, n_distinct):
