@@ -602,6 +602,46 @@ typedef struct zkgpu_open_req {
 } zkgpu_open_req;
 int zkgpu_gl_merkle_open_many(const zkgpu_open_req *req, uint32_t n);
 
+/* ---- circom .exec hand-off -----------------------------------------------------
+ * Circom*::getCommitedPols (main.recursive1.cpp:343-394, the same loop in main.cpp,
+ * main.recursive2.cpp and main.recursiveF.cpp): from a circom witness to the committed
+ * columns of C12a / recursive1 / recursive2 / recursiveF through the circuit's .exec file,
+ *     tmp[0 .. size_witness)  = witness
+ *     tmp[size_witness + i]   = tmp[idx_1] * c + tmp[idx_2] * d        add i = (idx_1, idx_2, c, d)
+ *     column j, row i         = sMap[n_cols i + j] ? tmp[sMap[n_cols i + j]] : 0     (i < nSMap)
+ *                               0                                                   (nSMap <= i < n)
+ * image: the .exec file's u64 words [nAdds, nSMap, adds[4 nAdds], sMap[nSMap n_cols]]
+ * (execFile.hpp:48-64).  sMap index 0 means "empty"; an add may read tmp[0].  Witness words and
+ * coefficients are any u64 (reduced mod p); the columns are canonical.
+ *
+ * zkgpu_exec_create plans once per circuit, on the host (csrc/exec_plan.hpp): the adds are
+ * levelled (an add's level is 1 + its operands' highest, witness slots 0) and sorted by level; a
+ * level of more than 1024 adds is one grid launch, a run of consecutive narrower levels one
+ * single-workgroup launch with a workgroup barrier between its levels; sMap is kept column-major
+ * as u32.  The tables and the tmp buffer (size_witness + nAdds words) are uploaded / allocated in
+ * one device block that lives in the handle.  The reference validates nothing; here ZKGPU_ERR_ARG
+ * with a message naming the add or cell refuses: image_words != 2 + 4 nAdds + nSMap n_cols; an add
+ * operand >= size_witness + i (a forward or self reference); an sMap entry >= size_witness +
+ * nAdds; size_witness + nAdds >= 2^32 (slots are u32); n_cols == 0 or size_witness == 0.
+ * zkgpu_exec_info: the counts, the schedule's depth, the kernel launches of one commit (the
+ * segments and the gather) and the device block's bytes; any out pointer may be null.
+ * zkgpu_exec_commit_dev: witness (host, size_witness words; free again when the call returns) ->
+ * column j at cols + j * ld (device), rows [0, n) of every column written, zeros included, rows
+ * [n, ld) untouched.  Queued on the library stream; the kernels are not waited for.  Refused:
+ * n < nSMap, n > ld, null pointers.  One commit at a time per handle (tmp is the handle's).
+ * zkgpu_exec_destroy waits for the library stream, then frees the block.
+ * zkgpu_exec_set_tail_width: the widest level a single-workgroup launch takes, for the plans of
+ * later zkgpu_exec_create calls (process-wide; 0: the default, 1024; above 1024: those calls are
+ * refused).  The columns do not depend on it (tools/exec_commit_cost.py compares 256 and 1024).
+ * There is no CPU path. */
+void zkgpu_exec_set_tail_width(uint32_t max_adds);
+int zkgpu_exec_create(void **exec, const uint64_t *image, uint64_t image_words, uint64_t size_witness,
+                      uint32_t n_cols);
+int zkgpu_exec_info(void *exec, uint64_t *n_adds, uint64_t *n_smap, uint32_t *n_levels, uint32_t *n_launches,
+                    uint64_t *device_bytes);
+int zkgpu_exec_commit_dev(void *exec, const uint64_t *witness, uint64_t *cols, uint64_t ld, uint64_t n);
+void zkgpu_exec_destroy(void *exec);
+
 /* ---- arithmetic self-test hook -----------------------------------------------
  * Runs one device field operation elementwise on arbitrary u64 inputs
  * (including non-canonical values >= p) and stores canonical results:

@@ -98,6 +98,23 @@ int zkgpu_stark_set_cm1(void *handle, const uint64_t *rows);
  * rank passes the whole row-major buffer and loads its own rows, as with
  * set_cm1. */
 int zkgpu_stark_set_cm1_async(void *handle, const uint64_t *rows);
+/* The recursion STARKs' way in (C12a, recursive1, recursive2, recursiveF: prover.cpp:591-593,
+ * 629-630, Circom*::getCommitedPols): the committed trace comes from a circom witness through the
+ * circuit's .exec file, on the GPU (zkgpu_exec_*, include/zkgpu.h) -- size_witness words cross
+ * PCIe instead of n x n_cm1.
+ * set_exec: once per circuit; image / image_words are the .exec file's u64 words, planned for
+ *   n_cm1 columns.  Refused with the planner's message (which names the add or cell), and when the
+ *   sMap has more than n rows.  The plan's tables and its tmp buffer are one device block outside
+ *   the memory plan (zkgpu_exec_info's device_bytes: 28 bytes an add, 4 a cell, 8 a slot); failing
+ *   to allocate it is an error.  A later set_exec replaces the plan.
+ * set_cm1_witness: witness (host, size_witness words, free again on return) -> cm1_n.  Leaves the
+ *   prover exactly as set_cm1 of the reference's buffer would, under either memory plan: prove,
+ *   audit and the constraint check may follow, a pending set_cm1_async load is superseded.  Its
+ *   wall time is the timer ZKGPU_EXEC_COMMIT: alone in zkgpu_stark_timers until the next proof,
+ *   then the last line of that proof's timers (outside STARK_TOTAL).
+ * Both are refused on a sharded handle; set_cm1_witness before set_exec. */
+int zkgpu_stark_set_exec(void *handle, const uint64_t *image, uint64_t image_words, uint64_t size_witness);
+int zkgpu_stark_set_cm1_witness(void *handle, const uint64_t *witness);
 /* cm1_n back into a host row-major buffer (n rows x n_cm1; the inverse of
  * set_cm1).  Single-GPU prover only. */
 int zkgpu_stark_get_cm1(void *handle, uint64_t *rows);

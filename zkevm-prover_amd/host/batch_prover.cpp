@@ -9,6 +9,10 @@
 //     zkevmCmPols         committed trace, N x nCm1 u64 rows (commit_pols.hpp)
 //     zkevmVerkey         optional {"constRoot": [...]} checked like the tree
 //     outputPath          directory for the outputs
+//   --circuit <prefix> reads <prefix>StarkInfo / ConstPols / ConstantsTree /
+//   Verkey / CmPols / Exec instead (config.cpp:243-259: c12a, recursive1,
+//   recursive2, recursivef); the default prefix is zkevm.
+//     <prefix>Exec        with --witness: the circuit's .exec file (execFile.hpp:48-64)
 //     zkgpuPublics        the public inputs as a JSON array (the publics.json
 //                         the reference writes, prover.cpp:657); genBatchProof
 //                         computes them from the executor's Main columns
@@ -22,8 +26,13 @@
 // step52ns), run as GPU programs (ProverInfo, host/stark_info.cpp); for the
 // zkEVM's parser bytecode, StepsGPU (host/zkgpu_steps.hpp) is the binding.
 //
-// Usage: zkgpu_batch_prover [--stream-trace] [--check-trace] [--audit] [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]]
+// Usage: zkgpu_batch_prover [--circuit PREFIX] [--witness FILE] [--stream-trace] [--check-trace] [--audit] [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]]
 //                           <config.json>
+//        (--witness: the committed trace comes from a circom witness, a raw file of sizeWitness
+//        little-endian u64 words, through <prefix>Exec on the GPU (zkgpu_stark_set_exec +
+//        zkgpu_stark_set_cm1_witness: Circom*::getCommitedPols, prover.cpp:591-593, 629-630) in
+//        place of the <prefix>CmPols file; .wtns parsing is not done here.  Single GPU; not with
+//        --stream-trace; --audit and --check-trace work with it)
 //        (--stream-trace: the trace file's rows stay in host memory and cross
 //        PCIe under stage 1 of the proof, zkgpu_stark_prove_from_rows; single GPU)
 //        (--check-trace: the constraint check in its STOP mode, zkgpu_stark_check_set:
@@ -133,11 +142,21 @@ static uint64_t flat_len(const zkgpu_stark_info &in)
     return L;
 }
 
-static void check_root(const char *what, const uint64_t got[4], const uint64_t want[4])
+static void check_root(const std::string &what, const uint64_t got[4], const uint64_t want[4], const std::string &prefix)
 {
     for (int i = 0; i < 4; i++)
         if (got[i] != want[i])
-            throw std::runtime_error(std::string(what) + ": constant root differs from the tree built from zkevmConstPols");
+            throw std::runtime_error(what + ": constant root differs from the tree built from " + prefix + "ConstPols");
+}
+
+// a raw file of little-endian u64 words, whatever their number
+static std::vector<uint64_t> read_u64_all(const std::string &path)
+{
+    const std::string b = read_text(path);
+    if (b.size() % 8) throw std::runtime_error(path + ": " + std::to_string(b.size()) + " bytes, not whole u64 words");
+    std::vector<uint64_t> v(b.size() / 8);
+    if (!v.empty()) memcpy(v.data(), b.data(), b.size());
+    return v;
 }
 
 struct Shard {
@@ -147,6 +166,8 @@ struct Shard {
     bool stream_trace = false;  // --stream-trace: zkgpu_stark_prove_from_rows instead of set_cm1 + prove
     bool check_trace = false;   // --check-trace: zkgpu_stark_check_set(ZKGPU_CHECK_STOP)
     bool audit = false;         // --audit: zkgpu_stark_audit instead of a proof
+    std::string circuit = "zkevm";  // --circuit: the prefix of the config keys
+    std::string witness;            // --witness: a circom witness file through <prefix>Exec instead of <prefix>CmPols
 };
 
 // --audit: the report as text (stdout) and as <dir>/trace_audit.json, the keys of zkgpu_audit_report
@@ -295,14 +316,23 @@ static int prove(const std::string &config_path, const Shard &sh)
 {
     const Value cfg = zkgpu::json::parse(read_text(config_path));
     auto key = [&](const char *k) { return cfg[k].string(); };
+    auto ckey = [&](const char *k) { return cfg[sh.circuit + k].string(); };  // the circuit's own files
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
-    const zkgpu::StarkInfo si = zkgpu::StarkInfo::from_file(key("zkevmStarkInfo"));
+    const zkgpu::StarkInfo si = zkgpu::StarkInfo::from_file(ckey("StarkInfo"));
     const zkgpu::ProverInfo pinfo(si);
     const zkgpu_stark_info &info = pinfo.info();
     const uint64_t N = 1ULL << info.n_bits;
-    const std::vector<uint64_t> consts = read_u64(key("zkevmConstPols"), N * info.n_const);
-    const std::vector<uint64_t> cm1 = read_u64(key("zkevmCmPols"), N * info.n_cm1);
+    const std::vector<uint64_t> consts = read_u64(ckey("ConstPols"), N * info.n_const);
+    const bool from_witness = !sh.witness.empty();
+    std::vector<uint64_t> cm1, witness, exec_image;
+    if (from_witness) {
+        exec_image = read_u64_all(ckey("Exec"));
+        witness = read_u64_all(sh.witness);
+        if (witness.empty()) throw std::runtime_error(sh.witness + ": an empty witness");
+    } else {
+        cm1 = read_u64(ckey("CmPols"), N * info.n_cm1);
+    }
     std::vector<uint64_t> publics(info.n_publics, 0);
     if (info.n_publics) publics = read_publics(key("zkgpuPublics"), info.n_publics);
 
@@ -348,24 +378,27 @@ static int prove(const std::string &config_path, const Shard &sh)
         ~Guard() { zkgpu_stark_destroy(h); }
     } guard{h};
     // (--stream-trace: the trace stays in host memory until the proof loads it under stage 1)
-    if (zkgpu_stark_set_const(h, consts.data()) || (!sh.stream_trace && zkgpu_stark_set_cm1(h, cm1.data())) ||
+    if (zkgpu_stark_set_const(h, consts.data()) ||
+        (from_witness && (zkgpu_stark_set_exec(h, exec_image.data(), exec_image.size(), witness.size()) ||
+                          zkgpu_stark_set_cm1_witness(h, witness.data()))) ||
+        (!from_witness && !sh.stream_trace && zkgpu_stark_set_cm1(h, cm1.data())) ||
         zkgpu_stark_set_publics(h, publics.data()))
         throw std::runtime_error(std::string("load: ") + zkgpu_stark_last_error());
     uint64_t verkey[4];
     zkgpu_stark_verkey(h, verkey);
     {
         // constant tree file: header, LDE, nodes; the root is its last 4 elements
-        const std::string t = read_text(key("zkevmConstantsTree"));
-        if (t.size() < 32 || t.size() % 8) throw std::runtime_error("zkevmConstantsTree: bad size");
+        const std::string t = read_text(ckey("ConstantsTree"));
+        if (t.size() < 32 || t.size() % 8) throw std::runtime_error(sh.circuit + "ConstantsTree: bad size");
         uint64_t root[4];
         memcpy(root, t.data() + t.size() - 32, 32);
-        check_root("zkevmConstantsTree", root, verkey);
+        check_root(sh.circuit + "ConstantsTree", root, verkey, sh.circuit);
     }
-    if (cfg.contains("zkevmVerkey")) {
-        const Value vk = zkgpu::json::parse(read_text(key("zkevmVerkey")));
+    if (cfg.contains(sh.circuit + "Verkey")) {
+        const Value vk = zkgpu::json::parse(read_text(ckey("Verkey")));
         uint64_t root[4];
         for (int i = 0; i < 4; i++) root[i] = vk["constRoot"][i].u64();
-        check_root("zkevmVerkey", root, verkey);
+        check_root(sh.circuit + "Verkey", root, verkey, sh.circuit);
     }
     if (sh.check_trace && zkgpu_stark_check_set(h, ZKGPU_CHECK_STOP))
         throw std::runtime_error(std::string("--check-trace: ") + zkgpu_stark_last_error());
@@ -441,6 +474,10 @@ int main(int argc, char **argv)
                 sh.comm = argv[a + 1];
             } else if (opt == "--device") {
                 sh.device = atoi(argv[a + 1]);
+            } else if (opt == "--circuit") {
+                sh.circuit = argv[a + 1];
+            } else if (opt == "--witness") {
+                sh.witness = argv[a + 1];
             } else {
                 break;
             }
@@ -450,6 +487,10 @@ int main(int argc, char **argv)
             throw std::runtime_error("--shard with WORLD > 1 needs --comm");
         if (sh.stream_trace && !sh.comm.empty())
             throw std::runtime_error("--stream-trace is for the single-GPU prover (no --comm)");
+        if (!sh.witness.empty() && sh.stream_trace)
+            throw std::runtime_error("--witness loads the trace on the GPU: not with --stream-trace (which streams the CmPols file)");
+        if (!sh.witness.empty() && (sh.world > 1 || !sh.comm.empty()))
+            throw std::runtime_error("--witness is for the single-GPU prover (not with --shard at WORLD > 1 or --comm)");
         if (sh.check_trace && sh.world > 1)
             throw std::runtime_error("--check-trace is for the single-GPU prover (not with --shard at WORLD > 1)");
         if (sh.audit && (sh.world > 1 || !sh.comm.empty()))
@@ -458,7 +499,7 @@ int main(int argc, char **argv)
             throw std::runtime_error("--audit runs no proof: not with --stream-trace or --check-trace");
         if (argc == a + 1 && argv[a][0] != '-') return prove(argv[a], sh);
         fprintf(stderr,
-                "usage: %s [--stream-trace] [--check-trace] [--audit] [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] "
+                "usage: %s [--circuit PREFIX] [--witness FILE] [--stream-trace] [--check-trace] [--audit] [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] "
                 "<config.json>\n"
                 "       %s --info <starkinfo.json>\n"
                 "       %s --zkin <starkinfo.json> <flat proof> <publics.json> <outdir>\n",

@@ -756,6 +756,15 @@ public:
         return fail("stark (sharded): prove_from_rows is single-GPU only (each rank loads its rows: set_cm1 / "
                     "set_cm1_async, then prove)");
     }
+    int set_exec(const uint64_t *, uint64_t, uint64_t) override
+    {
+        return fail("stark (sharded): set_exec is single-GPU only (the recursion circuits' traces fit one device)");
+    }
+    int set_cm1_witness(const uint64_t *) override
+    {
+        return fail("stark (sharded): set_cm1_witness is single-GPU only (the recursion circuits' traces fit one "
+                    "device)");
+    }
     uint64_t stream_stage_words() const override { return 0; }
 
     // the executor's row-major buffer: the rank takes rows [r0, r0 + ldn) mod N

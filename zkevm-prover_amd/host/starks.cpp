@@ -218,9 +218,14 @@ public:
     bool cm1_broken = false;
     // a whole trace has been loaded (set_cm1 / witness / a streamed or background load): the audit's precondition
     bool cm1_loaded = false;
+    // the circuit's .exec plan (set_exec) and the wall time of the last
+    // set_cm1_witness no proof has reported yet (< 0: none)
+    void *exec = nullptr;
+    double exec_commit_ms = -1.0;
 
     virtual ~Starks()
     {
+        if (exec) zkgpu_exec_destroy(exec);
         if (lowered_lde_batch) zkgpu_set_lde_batch_cols(0);
         for (void *t : cm1_ticket) (void)zkgpu_load_wait(t);
         probe_clear();
@@ -664,6 +669,50 @@ public:
         if (take_cm1_async(false)) return -1;  // a pending background load is superseded
         if (zkgpu_load_rows_dev(S.sec[SEC_CM1_N], N, rows, N, info.n_cm1, 0, 0))
             return fail("set_cm1: %s", zkgpu_last_error());
+        cm1_consumed = cm1_broken = false;
+        cm1_loaded = true;
+        return 0;
+    }
+
+    // The circuit's .exec hand-off (Circom*::getCommitedPols, prover.cpp:591-593,
+    // 629-630): planned for n_cm1 columns, its tables and tmp in a device block
+    // of their own outside the memory plan (zkgpu_exec_info reports the
+    // bytes), as the probe's block is.  A second call replaces the plan.
+    virtual int set_exec(const uint64_t *image, uint64_t image_words, uint64_t size_witness)
+    {
+        if (!image) return fail("set_exec: null argument");
+        if (!info.n_cm1) return fail("set_exec: the instance has no committed trace columns");
+        void *e = nullptr;
+        if (zkgpu_exec_create(&e, image, image_words, size_witness, info.n_cm1))
+            return fail("set_exec: %s", zkgpu_last_error());
+        uint64_t n_smap = 0;
+        (void)zkgpu_exec_info(e, nullptr, &n_smap, nullptr, nullptr, nullptr);
+        if (n_smap > N) {
+            zkgpu_exec_destroy(e);
+            return fail("set_exec: the sMap has %llu rows, the trace %llu", (unsigned long long)n_smap,
+                        (unsigned long long)N);
+        }
+        if (exec) zkgpu_exec_destroy(exec);
+        exec = e;
+        return 0;
+    }
+
+    // witness -> cm1_n through the plan of set_exec: the prover is left as
+    // set_cm1 of the reference's buffer leaves it
+    virtual int set_cm1_witness(const uint64_t *wit)
+    {
+        if (!exec) return fail("set_cm1_witness: no .exec plan is set; call set_exec first");
+        if (!wit) return fail("set_cm1_witness: null argument");
+        if (take_cm1_async(false)) return -1;  // a pending background load is superseded
+        const auto t = clk::now();
+        if (zkgpu_exec_commit_dev(exec, wit, S.sec[SEC_CM1_N], N, N) || zkgpu_synchronize()) {
+            cm1_broken = true;  // what the kernels reached of cm1_n is no whole trace
+            cm1_loaded = false;
+            return fail("set_cm1_witness: %s", zkgpu_last_error());
+        }
+        exec_commit_ms = std::chrono::duration<double, std::milli>(clk::now() - t).count();
+        timers.clear();
+        timers.emplace_back("ZKGPU_EXEC_COMMIT", exec_commit_ms);
         cm1_consumed = cm1_broken = false;
         cm1_loaded = true;
         return 0;
@@ -2052,6 +2101,10 @@ public:
         if (tr.err) return fail("transcript hashing failed: %s", zkgpu_last_error());
         if ((uint64_t)(w - out) != proof_len()) return fail("proof length mismatch");
         timers.emplace_back("STARK_TOTAL", std::chrono::duration<double, std::milli>(clk::now() - tall).count());
+        if (exec_commit_ms >= 0) {  // the hand-off that loaded this proof's trace (set_cm1_witness), outside the total
+            timers.emplace_back("ZKGPU_EXEC_COMMIT", exec_commit_ms);
+            exec_commit_ms = -1.0;
+        }
         return 0;
     }
 
@@ -2160,6 +2213,11 @@ int zkgpu_stark_witness(void *h) { return ((Starks *)h)->witness(); }
 int zkgpu_stark_set_cm1(void *h, const uint64_t *rows) { return ((Starks *)h)->set_cm1(rows); }
 int zkgpu_stark_set_cm1_async(void *h, const uint64_t *rows) { return ((Starks *)h)->set_cm1_async(rows); }
 int zkgpu_stark_get_cm1(void *h, uint64_t *rows) { return ((Starks *)h)->get_cm1(rows); }
+int zkgpu_stark_set_exec(void *h, const uint64_t *image, uint64_t image_words, uint64_t size_witness)
+{
+    return ((Starks *)h)->set_exec(image, image_words, size_witness);
+}
+int zkgpu_stark_set_cm1_witness(void *h, const uint64_t *witness) { return ((Starks *)h)->set_cm1_witness(witness); }
 int zkgpu_stark_set_const(void *h, const uint64_t *rows) { return ((Starks *)h)->set_const(rows); }
 int zkgpu_stark_set_publics(void *h, const uint64_t *publics) { return ((Starks *)h)->set_publics(publics); }
 uint64_t zkgpu_stark_proof_len(void *h) { return ((Starks *)h)->proof_len(); }

@@ -134,6 +134,11 @@ _SIGS = {
     "zkgpu_prof_kernels": (ctypes.c_int, [ctypes.c_char_p, u64]),
     "zkgpu_mark": (ctypes.c_int, [u32]),
     "zkgpu_mark_elapsed": (ctypes.c_int, [u32, u32, ctypes.POINTER(ctypes.c_double)]),
+    "zkgpu_exec_create": (ctypes.c_int, [ctypes.POINTER(vp), vp, u64, u64, u32]),
+    "zkgpu_exec_info": (ctypes.c_int, [vp, pu64, pu64, ctypes.POINTER(u32), ctypes.POINTER(u32), pu64]),
+    "zkgpu_exec_commit_dev": (ctypes.c_int, [vp, vp, vp, u64, u64]),
+    "zkgpu_exec_destroy": (None, [vp]),
+    "zkgpu_exec_set_tail_width": (None, [u32]),
     # include/zkgpu_parser.h (bindings in zkgpu/parser.py)
     "zkgpu_parser_convert": (ctypes.c_int, [u32, vp, u64, vp, u64, vp, u32, u32, u32, vp]),
     "zkgpu_steps_parser_eval": (ctypes.c_int, [u32, vp, u64, vp, u64, vp, u32, u32, u32, vp]),
@@ -957,6 +962,52 @@ def evmap_dev(cols, lds, dims, primes, lev, lpev, l_ld, n, extend_bits):
                                  dims_a.ctypes.data, pr_a.ctypes.data, n_ev, _addr(lev), _addr(lpev), l_ld, n,
                                  extend_bits), "zkgpu_evmap_dev")
     return out
+
+
+def exec_set_tail_width(max_adds):
+    """the widest level a single-workgroup launch takes in the plans of later
+    Exec(...) / set_exec calls (0: the default, 1024)"""
+    lib().zkgpu_exec_set_tail_width(max_adds)
+
+
+class Exec:
+    """A circom .exec hand-off planned for the GPU (zkgpu_exec_*): image is the
+    .exec file's u64 words (zkgpu.exec_file.make_image), size_witness and
+    n_cols come with it.  commit_dev(witness, cols, ld, n) queues witness ->
+    committed columns (column j at cols + j * ld, n rows each)."""
+
+    def __init__(self, image, size_witness, n_cols):
+        image = np.ascontiguousarray(image, dtype=np.uint64).reshape(-1)
+        self.size_witness, self.n_cols = int(size_witness), int(n_cols)
+        self.h = ctypes.c_void_p()
+        buf = image if image.size else np.zeros(1, np.uint64)
+        _check(lib().zkgpu_exec_create(ctypes.byref(self.h), buf.ctypes.data, image.size, self.size_witness,
+                                       self.n_cols), "zkgpu_exec_create")
+
+    def info(self):
+        """-> dict(n_adds, n_smap, n_levels, n_launches, device_bytes)"""
+        na, ns, by = u64(0), u64(0), u64(0)
+        nl, nk = u32(0), u32(0)
+        _check(lib().zkgpu_exec_info(self.h, ctypes.byref(na), ctypes.byref(ns), ctypes.byref(nl), ctypes.byref(nk),
+                                     ctypes.byref(by)), "zkgpu_exec_info")
+        return {"n_adds": na.value, "n_smap": ns.value, "n_levels": nl.value, "n_launches": nk.value,
+                "device_bytes": by.value}
+
+    def commit_dev(self, witness, cols, ld, n):
+        w = np.ascontiguousarray(witness, dtype=np.uint64).reshape(-1)
+        if w.size != self.size_witness:
+            raise ValueError("witness of %d words, size_witness is %d" % (w.size, self.size_witness))
+        _check(lib().zkgpu_exec_commit_dev(self.h, w.ctypes.data, _addr(cols), ld, n), "zkgpu_exec_commit_dev")
+
+    def close(self):
+        h, self.h = self.h, None
+        if h:
+            lib().zkgpu_exec_destroy(h)
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h and _lib is not None:
+            _lib.zkgpu_exec_destroy(h)
 
 
 # ---------------------------------------------------------------- profiling

@@ -128,6 +128,8 @@ def slib():
             ("zkgpu_stark_set_cm1", ctypes.c_int, [vp, vp]),
             ("zkgpu_stark_set_cm1_async", ctypes.c_int, [vp, vp]),
             ("zkgpu_stark_get_cm1", ctypes.c_int, [vp, vp]),
+            ("zkgpu_stark_set_exec", ctypes.c_int, [vp, vp, u64, u64]),
+            ("zkgpu_stark_set_cm1_witness", ctypes.c_int, [vp, vp]),
             ("zkgpu_stark_proof_len", u64, [vp]),
             ("zkgpu_stark_prove", ctypes.c_int, [vp, vp]),
             ("zkgpu_stark_prove_from_rows", ctypes.c_int, [vp, vp, ctypes.c_int, vp]),
@@ -407,6 +409,23 @@ class GpuStark:
     def set_cm1(self, rows):
         rows = np.ascontiguousarray(rows, np.uint64)
         _check(slib().zkgpu_stark_set_cm1(self.h, rows.ctypes.data), "zkgpu_stark_set_cm1")
+
+    def set_exec(self, image, size_witness):
+        """the circuit's .exec image (zkgpu.exec_file), planned for n_cm1 columns
+        (zkgpu_stark_set_exec); set_cm1_witness then loads a trace from a witness"""
+        image = np.ascontiguousarray(image, np.uint64).reshape(-1)
+        self._size_witness = int(size_witness)
+        buf = image if image.size else np.zeros(1, np.uint64)
+        _check(slib().zkgpu_stark_set_exec(self.h, buf.ctypes.data, image.size, self._size_witness),
+               "zkgpu_stark_set_exec")
+
+    def set_cm1_witness(self, witness):
+        """circom witness -> cm1_n on the GPU (zkgpu_stark_set_cm1_witness); as set_cm1 afterwards"""
+        w = np.ascontiguousarray(witness, np.uint64).reshape(-1)
+        sw = getattr(self, "_size_witness", None)
+        if sw is not None and w.size != sw:
+            raise ValueError("witness of %d words, size_witness is %d" % (w.size, sw))
+        _check(slib().zkgpu_stark_set_cm1_witness(self.h, w.ctypes.data), "zkgpu_stark_set_cm1_witness")
 
     def get_cm1(self):
         """cm1_n as the executor's row-major buffer (n x n_cm1)"""
