@@ -577,6 +577,50 @@ uint64_t zkgpu_lookup_misses_workspace_bytes(uint64_t n);
 int zkgpu_lookup_misses_dev(uint64_t *out, const uint64_t *f, uint64_t f_ld, const uint64_t *t, uint64_t t_ld,
                             uint64_t n, uint32_t dim, uint32_t max_vals);
 
+/* The cells that a connection check {a[0..k-1]} connect {S[0..k-1]} leaves unequal (the prover's
+ * trace audit, include/zkgpu_stark.h zkgpu_stark_conn_check: the third answer beside
+ * zkgpu_lookup_misses_dev and zkgpu_multiset_diff_dev).  On the trace domain of n = 2^n_bits rows
+ * with generator w (the NTT's), cell (j, r) has the identity ks[j] w^r and the constant column
+ * S_i holds at row r the identity of the cell that (i, r) is wired to; the grand product closes
+ * exactly when S names every cell once and every cell holds the value of the cell it is wired to.
+ * a and s are column-major sections with leading dimensions a_ld and s_ld; a_cols and s_cols
+ * (host, k entries each, NULL: 0 .. k-1) list the k columns of each.  ks (host, k values, NULL:
+ * 1, 12, 144, ... = 12^i) are the coset shifts.  ASSUMPTION: the default is pil-stark's getKs
+ * with k = 12; a caller whose constants were built with other shifts passes them.
+ * A cell is the number i n + r, i the index into the column lists.  out (device,
+ * 3 + 6 * max_vals words):
+ *   out[0]  broken cells: S_i[r] is the identity of a cell t and a(i, r) != a(t) mod p.  One
+ *           wrong cell inside a cycle is two broken links, both naming it; a cell wired to itself
+ *           never breaks
+ *   out[1]  foreign cells: S_i[r] is no ks[j] w^r' (a damaged or mismatched constant file)
+ *   out[2]  untargeted cells: no S value names them.  0 exactly when S, with no foreign cell, is a
+ *           permutation of the cells
+ *   then max_vals records {cell, target cell, value at cell, value at target} of the broken
+ *   cells, ascending by cell, values canonical; {UINT64_MAX, 0, 0, 0} past the last
+ *   then max_vals records {cell, S value} of the foreign cells; {UINT64_MAX, 0} past the last
+ * None of this depends on a challenge.  Inputs may be non-canonical: v and v + p are one value,
+ * S values too.  The result does not depend on the launch geometry: the target of an S value is
+ * computed (v^n names the coset, the row comes out bit by bit in the subgroup of order 2^n_bits),
+ * not looked up, every cell writes its own two flags, the marks of the named cells are idempotent
+ * stores, the lists come from the reduction of zkgpu_nonzero_rows_dev over a flag per cell, and
+ * out[2] is a sum added up per workgroup before one atomic each.  Enqueued on the library
+ * stream, no host synchronisation; rows [n, ld) are not read.  ZKGPU_ERR_ARG, nothing queued (and
+ * judged before the library's state, so a refusal needs no GPU): a_ld < n or s_ld < n, k = 0 or
+ * k > 64, k n > 2^31, max_vals > 4096, n_bits > 28, a column repeated within a list, a zero in
+ * ks or two cosets that collide ((ks[i] / ks[j])^n = 1, "the cosets of ks[i] and ks[j]
+ * collide"), null pointers.
+ * Scratch: the grow-only workspace of the plookup, of
+ *   zkgpu_conn_breaks_workspace_bytes(n, k)
+ *     = 16 c + 8 ceil(c / 2) + 8 ceil(ceil(c / 1024) / 2) + 16 * 4097 + 8,  c = k n
+ * bytes: two flag columns of c u64, c u32 marks, the reduction's block counts, the two cell
+ * lists and the word out[2] adds up in (host only, no GPU needed).
+ * zkgpu_conn_ks_check judges k, n_bits and ks alone, with the same messages (host only). */
+uint64_t zkgpu_conn_breaks_workspace_bytes(uint64_t n, uint32_t k);
+int zkgpu_conn_ks_check(const uint64_t *ks, uint32_t k, uint32_t n_bits);
+int zkgpu_conn_breaks_dev(uint64_t *out, const uint64_t *a, uint64_t a_ld, const uint32_t *a_cols, const uint64_t *s,
+                          uint64_t s_ld, const uint32_t *s_cols, uint32_t k, const uint64_t *ks, uint32_t n_bits,
+                          uint32_t max_vals);
+
 /* 3 ext columns (ld >= n) -> interleaved n x 3 (the FRI polynomial layout, friProve.cpp) */
 int zkgpu_cols3_to_interleaved_dev(uint64_t *out, const uint64_t *cols, uint64_t ld, uint64_t n);
 

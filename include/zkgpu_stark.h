@@ -294,8 +294,10 @@ int zkgpu_stark_check_named(void *handle, uint32_t slot, uint32_t *ids, uint64_t
  * What the lists mean: for a permutation check (num = f + gamma, den = t + gamma) they are
  * exactly the offending values and where they first occur -- a tuple on one side only, or a
  * default value with one copy too many ("5000001 times against 5000000").  The per-row factors of
- * a plookup or a connection product are not paired values: there the lists say only that the two
- * columns differ.
+ * a plookup or a connection product are not paired values, so there the lists do not name the
+ * fault: a plookup's missing values come from zkgpu_lookup_misses_dev (layer A of the audit
+ * below), a connection's unequal cells from zkgpu_stark_conn_check / zkgpu_stark_audit_conn
+ * (below).
  * A proof whose products all close queues nothing of this: no kernel, no allocation, the same
  * timers, the same proof; nothing is added to either memory plan's figure (the comparison's
  * scratch is the library workspace, zkgpu_multiset_diff_workspace_bytes(n), taken on the failing
@@ -385,6 +387,53 @@ int zkgpu_stark_audit(void *handle, uint32_t flags, zkgpu_audit_report *out);
  * messages; returns the length the whole text needs (without the terminator), at most len - 1
  * characters are written; fails when no audit has run on the handle */
 int zkgpu_stark_audit_format(void *handle, char *buf, uint64_t len);
+
+/* ---- connection checks: the cells a copy constraint leaves unequal
+ * A plonk-style circuit (C12a, recursive1, recursive2) asserts nearly everything about its
+ * witness through one connection check {a[0..k-1]} connect {S[0..k-1]} (the starkinfo's ciCtx):
+ * cell (i, r) of committed column a_i must hold the value of the cell that the constant column
+ * S_i names at row r (include/zkgpu.h zkgpu_conn_breaks_dev: identities, coset shifts ks and
+ * what broken, foreign and untargeted mean).  When its grand product does not close, what a
+ * developer needs is which two wired cells differ; the product's num / den lists cannot say.
+ *   conn_set    declares product z of zctx as the connection of the k cm1 columns cm1_cols with
+ *               the k constant columns const_cols (the starkinfo carries expression ids only, so
+ *               the caller tells them) and the shifts ks (NULL: 12^i, pil-stark's getKs with
+ *               k = 12 -- an assumption, see zkgpu_conn_breaks_dev).  The description is copied;
+ *               d = NULL clears the declaration.  Refused: z >= n_zctx, a column past n_cm1 /
+ *               n_const or repeated, k = 0 or > 64, ks with a zero or colliding cosets.
+ *   conn_check  runs the primitive over cm1_n and const_n of the loaded trace and returns the
+ *               report: no stage program, no challenge, one synchronisation; the trace is not
+ *               touched and nothing is added to either memory plan (the scratch is the library
+ *               workspace, zkgpu_conn_breaks_workspace_bytes(n, k)).  Needs a whole trace
+ *               loaded, as the audit; refused for an undeclared product.
+ *   audit       (zkgpu_stark_audit, layer B) for each LISTED open product with a declared
+ *               connection the same routine runs and its report is kept; a closed product queues
+ *               nothing, and a prover with no declaration audits exactly as before.  The
+ *               zkgpu_audit_report keeps its layout: audit_conn(k) returns the report that goes
+ *               with report.z[k] of the last audit, ran = 0 when that entry is no declared
+ *               connection, is not listed, or the scratch could not be had.
+ * In a report col / to_col are indices into the declaration's column lists (pols[i]), rows are
+ * trace rows, values canonical.  breaks holds the lowest ZKGPU_CONN_MAX broken cells by (col,
+ * row), {UINT32_MAX, 0, UINT64_MAX, 0, 0, 0} past the last; foreign likewise, {UINT32_MAX,
+ * UINT64_MAX, 0} past the last.  One wrong cell inside a cycle is two entries, both naming it.
+ * zkgpu_stark_audit_format prints, under the product's calculateZ line,
+ *   "  connection: 2 cell(s) differ from the cell they are wired to; pols[1] row 37 (= 5) is
+ *    wired to pols[0] row 28 (= 6)", one line per listed break, "and N more", and the foreign
+ * and untargeted counts when they are not zero.
+ * The proving path (prove's own calculateZ failure) is unchanged.  Single-GPU provers only. */
+typedef struct { uint32_t k; const uint32_t *cm1_cols, *const_cols; const uint64_t *ks; } zkgpu_conn_desc;
+int zkgpu_stark_conn_set(void *handle, uint32_t z, const zkgpu_conn_desc *d);
+#define ZKGPU_CONN_MAX 16
+typedef struct { uint32_t col, to_col; uint64_t row, to_row, value, to_value; } zkgpu_conn_break;
+typedef struct { uint32_t col; uint64_t row, s_value; } zkgpu_conn_foreign;
+typedef struct {
+    uint32_t ran, z;  /* 1: the primitive ran; the product (index into zctx) */
+    uint64_t n_broken, n_foreign, n_untargeted;
+    zkgpu_conn_break breaks[ZKGPU_CONN_MAX];
+    zkgpu_conn_foreign foreign[ZKGPU_CONN_MAX];
+} zkgpu_conn_report;
+int zkgpu_stark_conn_check(void *handle, uint32_t z, zkgpu_conn_report *out);
+int zkgpu_stark_audit_conn(void *handle, uint32_t k, zkgpu_conn_report *out);
 
 /* ---- the Fiat-Shamir transcript the prover runs on the host, as the
  * reference's class Transcript (transcript.hpp:14-37, transcript.cpp:4-88):

@@ -26,7 +26,7 @@
 // step52ns), run as GPU programs (ProverInfo, host/stark_info.cpp); for the
 // zkEVM's parser bytecode, StepsGPU (host/zkgpu_steps.hpp) is the binding.
 //
-// Usage: zkgpu_batch_prover [--circuit PREFIX] [--witness FILE] [--stream-trace] [--check-trace] [--audit] [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]]
+// Usage: zkgpu_batch_prover [--circuit PREFIX] [--witness FILE] [--stream-trace] [--check-trace] [--audit [--connections FILE]] [--shard RANK/WORLD --comm rccl:<id file>|host:</shm name> [--device D]]
 //                           <config.json>
 //        (--witness: the committed trace comes from a circom witness, a raw file of sizeWitness
 //        little-endian u64 words, through <prefix>Exec on the GPU (zkgpu_stark_set_exec +
@@ -46,6 +46,12 @@
 //        context; the report on stdout and in <outputPath>/trace_audit.json, no proof file;
 //        status 0 for a clean trace, 3 for one with findings.  Not a verifier: the audit's
 //        challenges do not depend on the trace (include/zkgpu_stark.h).  Single GPU)
+//        (--connections FILE, with --audit: [{"ciCtx": i, "pols": [cm1 columns], "S": [constant
+//        columns], "ks": [optional coset shifts]}] tells the columns of each connection check --
+//        the starkinfo carries only expression ids -- so that an open connection product names
+//        the cells that differ from the cell they are wired to (zkgpu_stark_conn_set): the lines
+//        follow the product's in the report, with pols[i] beside the cm1 column, are repeated on
+//        stderr, and trace_audit.json gains "connection" in the product's entry)
 //        (--shard: one rank of ONE proof row-sharded over WORLD processes,
 //        zkgpu_stark_create_sharded; every rank runs this command with the
 //        same config, rank 0 writes the outputs.  rccl: rank 0 writes the
@@ -63,6 +69,7 @@
 #include <chrono>
 #include <cstdio>
 #include <fstream>
+#include <map>
 #include <memory>
 #include <thread>
 #include <sstream>
@@ -168,12 +175,54 @@ struct Shard {
     bool audit = false;         // --audit: zkgpu_stark_audit instead of a proof
     std::string circuit = "zkevm";  // --circuit: the prefix of the config keys
     std::string witness;            // --witness: a circom witness file through <prefix>Exec instead of <prefix>CmPols
+    std::string connections;        // --connections: the wiring's columns of each ciCtx entry, for --audit
 };
+
+// --connections <file.json>: [{"ciCtx": i, "pols": [cm1 columns], "S": [constant columns], "ks": [optional]}].
+// The starkinfo carries only expression ids under ciCtx, so the columns of the wiring are told here.
+// Each entry declares its product (the driver's order puCtx, peCtx, ciCtx) a connection
+// (zkgpu_stark_conn_set); returns product -> cm1 columns.  A malformed entry is refused by its index.
+static std::map<uint32_t, std::vector<uint32_t>> declare_connections(void *h, const zkgpu::StarkInfo &si,
+                                                                     const std::string &path)
+{
+    std::map<uint32_t, std::vector<uint32_t>> pols_of;
+    const Value j = zkgpu::json::parse(read_text(path));
+    if (j.kind != Value::Array) throw std::runtime_error("--connections: " + path + ": not a list of entries");
+    for (size_t i = 0; i < j.size(); i++) {
+        const std::string who = "--connections: entry " + std::to_string(i) + ": ";
+        try {
+            const Value &e = j[i];
+            const uint64_t ci = e["ciCtx"].u64();
+            if (ci >= si.ciCtx.size())
+                throw std::runtime_error("ciCtx " + std::to_string(ci) + ": the starkinfo has " +
+                                         std::to_string(si.ciCtx.size()) + " connection check(s)");
+            const uint32_t z = (uint32_t)(si.puCtx.size() + si.peCtx.size() + ci);
+            if (pols_of.count(z)) throw std::runtime_error("ciCtx " + std::to_string(ci) + " is declared twice");
+            std::vector<uint32_t> pols, S;
+            std::vector<uint64_t> ks;
+            for (size_t k = 0; k < e["pols"].size(); k++) pols.push_back((uint32_t)e["pols"][k].u64());
+            for (size_t k = 0; k < e["S"].size(); k++) S.push_back((uint32_t)e["S"][k].u64());
+            if (e.contains("ks"))
+                for (size_t k = 0; k < e["ks"].size(); k++) ks.push_back(e["ks"][k].u64());
+            if (pols.empty() || pols.size() != S.size() || (e.contains("ks") && ks.size() != pols.size()))
+                throw std::runtime_error("\"pols\", \"S\" and \"ks\" must be lists of one length, not empty (" +
+                                         std::to_string(pols.size()) + ", " + std::to_string(S.size()) +
+                                         (e.contains("ks") ? ", " + std::to_string(ks.size()) : "") + ")");
+            const zkgpu_conn_desc d = {(uint32_t)pols.size(), pols.data(), S.data(), ks.empty() ? nullptr : ks.data()};
+            if (zkgpu_stark_conn_set(h, z, &d)) throw std::runtime_error(zkgpu_stark_last_error());
+            pols_of[z] = pols;
+        } catch (const std::exception &x) {
+            throw std::runtime_error(who + x.what());
+        }
+    }
+    return pols_of;
+}
 
 // --audit: the report as text (stdout) and as <dir>/trace_audit.json, the keys of zkgpu_audit_report
 // plus each finding's starkinfo context and, per listed failing row, the failing term ids.  The
 // driver's products come in the order puCtx, peCtx, ciCtx: product k < nPu is plookup k's.
-static int audit_trace(void *h, const zkgpu::StarkInfo &si, const zkgpu_stark_info &info, const std::string &dir)
+static int audit_trace(void *h, const zkgpu::StarkInfo &si, const zkgpu_stark_info &info, const std::string &dir,
+                       const std::map<uint32_t, std::vector<uint32_t>> &conn_pols)
 {
     zkgpu_audit_report r;
     if (zkgpu_stark_audit(h, ZKGPU_AUDIT_NAMES, &r)) throw std::runtime_error(std::string("audit: ") + zkgpu_stark_last_error());
@@ -185,6 +234,13 @@ static int audit_trace(void *h, const zkgpu::StarkInfo &si, const zkgpu_stark_in
     for (uint32_t z = 0; z < info.n_zctx; z++) {
         c.z_label.push_back(si.z_context(z));
         c.z_plookup.push_back(z < info.n_pu ? (int32_t)z : -1);
+    }
+    // a declared connection prints its cells as pols[i] beside the cm1 column
+    for (const auto &kv : conn_pols) {
+        if (c.conn_col_label.size() <= kv.first) c.conn_col_label.resize(kv.first + 1);
+        for (size_t i = 0; i < kv.second.size(); i++)
+            c.conn_col_label[kv.first].push_back("pols[" + std::to_string(i) + "] (cm1 column " +
+                                                 std::to_string(kv.second[i]) + ")");
     }
     auto str = [](uint64_t v) { return Value::str(std::to_string(v % 0xFFFFFFFF00000001ULL)); };
     Value j = Value::object();
@@ -233,6 +289,41 @@ static int audit_trace(void *h, const zkgpu::StarkInfo &si, const zkgpu_stark_in
                 l.push(t);
             }
             o.set(side ? "den" : "num", l);
+        }
+        // the cells a declared connection leaves unequal (zkgpu_stark_audit_conn), on stderr as well
+        zkgpu_conn_report cr;
+        if (zkgpu_stark_audit_conn(h, k, &cr)) throw std::runtime_error(std::string("audit: ") + zkgpu_stark_last_error());
+        c.conn.push_back(cr);
+        if (cr.ran) {
+            Value q = Value::object(), br = Value::array(), fo = Value::array();
+            q.set("n_broken", Value::num(cr.n_broken));
+            q.set("n_foreign", Value::num(cr.n_foreign));
+            q.set("n_untargeted", Value::num(cr.n_untargeted));
+            for (const zkgpu_conn_break &b : cr.breaks) {
+                if (b.row == UINT64_MAX) break;
+                Value t = Value::array();
+                t.push(Value::num(b.col));
+                t.push(Value::num(b.row));
+                t.push(Value::num(b.to_col));
+                t.push(Value::num(b.to_row));
+                t.push(str(b.value));
+                t.push(str(b.to_value));
+                br.push(t);
+            }
+            for (const zkgpu_conn_foreign &f : cr.foreign) {
+                if (f.row == UINT64_MAX) break;
+                Value t = Value::array();
+                t.push(Value::num(f.col));
+                t.push(Value::num(f.row));
+                t.push(str(f.s_value));
+                fo.push(t);
+            }
+            q.set("breaks", br);
+            q.set("foreign", fo);
+            o.set("connection", q);
+            fprintf(stderr, "zkgpu_batch_prover: grand product %u is %s\n%s", e.z, si.z_context(e.z).c_str(),
+                    zkgpu_host::audit_detail::conn_lines(
+                        cr, e.z < c.conn_col_label.size() ? &c.conn_col_label[e.z] : nullptr).c_str());
         }
         zs.push(o);
     }
@@ -406,7 +497,11 @@ static int prove(const std::string &config_path, const Shard &sh)
     if (sh.check_trace && zkgpu_stark_check_names_set(h, 1))
         fprintf(stderr, "--check-trace: %s; the failing rows will be named, not the identities\n",
                 zkgpu_stark_last_error());
-    if (sh.audit) return audit_trace(h, si, info, key("outputPath"));
+    if (sh.audit) {
+        std::map<uint32_t, std::vector<uint32_t>> conn_pols;
+        if (!sh.connections.empty()) conn_pols = declare_connections(h, si, sh.connections);
+        return audit_trace(h, si, info, key("outputPath"), conn_pols);
+    }
     const auto t1 = clk::now();
     const uint64_t len = zkgpu_stark_proof_len(h);
     if (len != flat_len(info)) throw std::runtime_error("proof length mismatch");
@@ -478,6 +573,8 @@ int main(int argc, char **argv)
                 sh.circuit = argv[a + 1];
             } else if (opt == "--witness") {
                 sh.witness = argv[a + 1];
+            } else if (opt == "--connections") {
+                sh.connections = argv[a + 1];
             } else {
                 break;
             }
@@ -497,9 +594,11 @@ int main(int argc, char **argv)
             throw std::runtime_error("--audit is for the single-GPU prover (not with --shard at WORLD > 1 or --comm)");
         if (sh.audit && (sh.stream_trace || sh.check_trace))
             throw std::runtime_error("--audit runs no proof: not with --stream-trace or --check-trace");
+        if (!sh.connections.empty() && !sh.audit)
+            throw std::runtime_error("--connections names the wiring for --audit: not without it");
         if (argc == a + 1 && argv[a][0] != '-') return prove(argv[a], sh);
         fprintf(stderr,
-                "usage: %s [--circuit PREFIX] [--witness FILE] [--stream-trace] [--check-trace] [--audit] [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] "
+                "usage: %s [--circuit PREFIX] [--witness FILE] [--stream-trace] [--check-trace] [--audit [--connections FILE]] [--shard RANK/WORLD --comm rccl:<file>|host:</name> [--device D]] "
                 "<config.json>\n"
                 "       %s --info <starkinfo.json>\n"
                 "       %s --zkin <starkinfo.json> <flat proof> <publics.json> <outdir>\n",

@@ -747,6 +747,19 @@ public:
     {
         return fail("stark (sharded): audit_format: single-GPU provers only");
     }
+    int conn_set(uint32_t, const zkgpu_conn_desc *) override
+    {
+        return fail("stark (sharded): conn_set: single-GPU provers only (as the audit)");
+    }
+    int conn_check(uint32_t, zkgpu_conn_report *) override
+    {
+        return fail("stark (sharded): conn_check: single-GPU provers only (a rank holds a row block of the n-domain "
+                    "sections)");
+    }
+    int audit_conn(uint32_t, zkgpu_conn_report *) const override
+    {
+        return fail("stark (sharded): audit_conn: single-GPU provers only");
+    }
     int check_names_set(int) override
     {
         return fail("stark (sharded): check_names_set is single-GPU only (as check_set)");

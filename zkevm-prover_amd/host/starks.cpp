@@ -1712,8 +1712,8 @@ public:
     // zdiag before the failure returns.  For a permutation check (num = f +
     // gamma, den = t + gamma) the lists are the offending values and where
     // they first occur; the per-row factors of a plookup or connection
-    // product are not paired values, there the lists say only that the
-    // columns differ.  The 98-word result block lives for this call only.
+    // product are not paired values: those faults are named by the audit's
+    // lookup misses and by conn_check / audit_conn below.  The 98-word result block lives for this call only.
     zkgpu_z_diag zdiag = {};
 
     int z_open(uint32_t z, uint32_t n_open)
@@ -1808,19 +1808,122 @@ public:
         return 0;
     }
 
+    // ---- connection checks (include/zkgpu_stark.h zkgpu_stark_conn_set): product z of zctx declared as
+    // {cm1 columns} connect {constant columns}; conn_run names the cells that keep it open
+    // (zkgpu_conn_breaks_dev over cm1_n and const_n, one synchronisation, a 99-word result block
+    // that lives for the call).  Neither section is written.
+    struct ConnDecl {
+        std::vector<uint32_t> cm1_cols, const_cols;
+        std::vector<uint64_t> ks;  // empty: the default shifts
+    };
+    std::map<uint32_t, ConnDecl> conns;
+    zkgpu_conn_report audit_conns[ZKGPU_AUDIT_MAX_Z] = {};  // by index into audit_rep.z
+
+    virtual int conn_set(uint32_t z, const zkgpu_conn_desc *d)
+    {
+        if (z >= info.n_zctx) return fail("conn_set: product %u: the instance has %u grand product(s)", z, info.n_zctx);
+        if (!d) {
+            conns.erase(z);
+            return 0;
+        }
+        if (!d->cm1_cols || !d->const_cols) return fail("conn_set: product %u: null column list", z);
+        if (zkgpu_conn_ks_check(d->ks, d->k, info.n_bits)) return fail("conn_set: product %u: %s", z, zkgpu_last_error());
+        ConnDecl c;
+        for (uint32_t i = 0; i < d->k; i++) {
+            if (d->cm1_cols[i] >= info.n_cm1)
+                return fail("conn_set: product %u: cm1 column %u: the instance has %u", z, d->cm1_cols[i], info.n_cm1);
+            if (d->const_cols[i] >= info.n_const)
+                return fail("conn_set: product %u: constant column %u: the instance has %u", z, d->const_cols[i],
+                            info.n_const);
+            for (uint32_t j = 0; j < i; j++)
+                if (d->cm1_cols[j] == d->cm1_cols[i] || d->const_cols[j] == d->const_cols[i])
+                    return fail("conn_set: product %u: column %u repeated", z,
+                                d->cm1_cols[j] == d->cm1_cols[i] ? d->cm1_cols[i] : d->const_cols[i]);
+        }
+        c.cm1_cols.assign(d->cm1_cols, d->cm1_cols + d->k);
+        c.const_cols.assign(d->const_cols, d->const_cols + d->k);
+        if (d->ks) c.ks.assign(d->ks, d->ks + d->k);
+        conns[z] = std::move(c);
+        return 0;
+    }
+
+    int conn_run(uint32_t z, const ConnDecl &c, zkgpu_conn_report &r, std::string &why)
+    {
+        constexpr uint32_t M = ZKGPU_CONN_MAX;
+        uint64_t h[3 + 6 * M];
+        void *dev = nullptr;
+        const uint32_t k = (uint32_t)c.cm1_cols.size();
+        int rc = zkgpu_dev_malloc(&dev, sizeof h);
+        if (!rc)
+            rc = zkgpu_conn_breaks_dev((uint64_t *)dev, S.sec[SEC_CM1_N], N, c.cm1_cols.data(), S.sec[SEC_CONST_N], N,
+                                       c.const_cols.data(), k, c.ks.empty() ? nullptr : c.ks.data(), info.n_bits, M);
+        if (!rc) rc = zkgpu_memcpy_d2h(h, dev, sizeof h);
+        why = rc ? zkgpu_last_error() : "";
+        (void)zkgpu_dev_free(dev);
+        if (rc) return rc;
+        r = zkgpu_conn_report{};
+        r.ran = 1;
+        r.z = z;
+        r.n_broken = h[0], r.n_foreign = h[1], r.n_untargeted = h[2];
+        for (uint32_t e = 0; e < M; e++) {
+            const uint64_t *b = h + 3 + 4 * e, *f = h + 3 + 4 * M + 2 * e;
+            zkgpu_conn_break &o = r.breaks[e];
+            if (b[0] == UINT64_MAX)
+                o = {UINT32_MAX, 0, UINT64_MAX, 0, 0, 0};
+            else
+                o = {(uint32_t)(b[0] >> info.n_bits), (uint32_t)(b[1] >> info.n_bits), b[0] & (N - 1), b[1] & (N - 1),
+                     b[2], b[3]};
+            if (f[0] == UINT64_MAX)
+                r.foreign[e] = {UINT32_MAX, UINT64_MAX, 0};
+            else
+                r.foreign[e] = {(uint32_t)(f[0] >> info.n_bits), f[0] & (N - 1), f[1]};
+        }
+        return 0;
+    }
+
+    // the audit's preconditions, in its words
+    int need_trace(const char *who)
+    {
+        if (cm1_broken)
+            return fail("%s: the last streamed load (prove_from_rows) failed part-way: no whole trace is loaded; "
+                        "load one with set_cm1 or witness first", who);
+        if (lean() && cm1_consumed)
+            return fail("%s: the previous proof consumed the trace (lean memory plan: cm1_n is extended in place); "
+                        "load the next one with set_cm1 or witness first", who);
+        if (!cm1_loaded) return fail("%s: no trace is loaded; load one with set_cm1 or witness first", who);
+        return 0;
+    }
+
+    virtual int conn_check(uint32_t z, zkgpu_conn_report *out)
+    {
+        if (!out) return fail("conn_check: null buffer");
+        if (z >= info.n_zctx)
+            return fail("conn_check: product %u: the instance has %u grand product(s)", z, info.n_zctx);
+        const auto it = conns.find(z);
+        if (it == conns.end()) return fail("conn_check: product %u is not declared a connection (conn_set)", z);
+        if (need_trace("conn_check")) return -1;
+        std::string why;
+        if (conn_run(z, it->second, *out, why)) return fail("conn_check: product %u: %s", z, why.c_str());
+        return 0;
+    }
+
+    virtual int audit_conn(uint32_t k, zkgpu_conn_report *out) const
+    {
+        if (!out) return fail("audit_conn: null buffer");
+        if (!audit_valid) return fail("audit_conn: no audit has run on this prover");
+        if (k >= ZKGPU_AUDIT_MAX_Z) return fail("audit_conn: entry %u: the report lists %u", k, ZKGPU_AUDIT_MAX_Z);
+        *out = audit_conns[k];
+        return 0;
+    }
+
     virtual int audit(uint32_t flags, zkgpu_audit_report *out)
     {
         if (!out) return fail("audit: null buffer");
         if (flags & ~ZKGPU_AUDIT_NAMES) return fail("audit: unknown flags 0x%x", flags);
-        if (cm1_broken)
-            return fail("audit: the last streamed load (prove_from_rows) failed part-way: no whole trace is loaded; "
-                        "load one with set_cm1 or witness first");
-        if (lean() && cm1_consumed)
-            return fail("audit: the previous proof consumed the trace (lean memory plan: cm1_n is extended in place); "
-                        "load the next one with set_cm1 or witness first");
-        if (!cm1_loaded) return fail("audit: no trace is loaded; load one with set_cm1 or witness first");
+        if (need_trace("audit")) return -1;
         audit_valid = false;
         audit_rep = zkgpu_audit_report{};
+        for (zkgpu_conn_report &c : audit_conns) c = zkgpu_conn_report{};
         audit_why.clear();
         check_pending = false;
         check_res = zkgpu_check_result{};
@@ -1894,6 +1997,9 @@ public:
                 // the product is still listed
                 std::string why;
                 e.compared = z_compare(z, e.n_num, e.n_den, e.num, e.den, why);
+                // a declared connection: the cells that keep it open (ran = 0 without the scratch, as compared)
+                const auto it = conns.find(z);
+                if (it != conns.end()) (void)conn_run(z, it->second, audit_conns[R.n_z_open - 1], why);
             }
         }
         if (tstop("AUDIT_Z")) return -1;
@@ -1948,6 +2054,7 @@ public:
         c.identities_why = audit_why;
         c.named = audit_named;
         c.term_ids = audit_terms;
+        c.conn.assign(audit_conns, audit_conns + ZKGPU_AUDIT_MAX_Z);
         const std::string s = zkgpu_host::audit_format(audit_rep, c);
         if (len) {
             const size_t n = std::min<size_t>(s.size(), len - 1);
@@ -2266,6 +2373,9 @@ int zkgpu_stark_check_result(void *h, zkgpu_check_result *out) { return ((Starks
 int zkgpu_stark_z_diag(void *h, zkgpu_z_diag *out) { return ((Starks *)h)->z_diag(out); }
 int zkgpu_stark_audit(void *h, uint32_t flags, zkgpu_audit_report *out) { return ((Starks *)h)->audit(flags, out); }
 int zkgpu_stark_audit_format(void *h, char *buf, uint64_t len) { return ((Starks *)h)->audit_format(buf, len); }
+int zkgpu_stark_conn_set(void *h, uint32_t z, const zkgpu_conn_desc *d) { return ((Starks *)h)->conn_set(z, d); }
+int zkgpu_stark_conn_check(void *h, uint32_t z, zkgpu_conn_report *out) { return ((Starks *)h)->conn_check(z, out); }
+int zkgpu_stark_audit_conn(void *h, uint32_t k, zkgpu_conn_report *out) { return ((Starks *)h)->audit_conn(k, out); }
 int zkgpu_stark_check_names_set(void *h, int on) { return ((Starks *)h)->check_names_set(on); }
 int zkgpu_stark_check_terms(void *h, zxp_split_term *out, uint32_t max, uint32_t *n)
 {

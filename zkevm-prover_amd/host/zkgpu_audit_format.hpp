@@ -28,6 +28,12 @@ struct AuditContext {
     // with naming: the failing term ids of each listed row (identities.rows order)
     bool named = false;
     std::vector<std::vector<uint32_t>> term_ids;
+    // optional, by index into the report's z list: the connection report that goes with the entry
+    // (zkgpu_stark_audit_conn; ran = 0: none)
+    std::vector<zkgpu_conn_report> conn;
+    // optional, by product index, then by index into the connection's column lists:
+    // "pols[1] (cm1 column 7)"; a missing or empty entry prints as "pols[1]"
+    std::vector<std::vector<std::string>> conn_col_label;
 };
 
 namespace audit_detail {
@@ -37,6 +43,45 @@ inline std::string side(const char *name, uint64_t cnt, const zkgpu_z_diag_val &
     if (!cnt) return std::string("no value of ") + name + " unmatched";
     return u(cnt) + " value(s) of " + name + " unmatched, the first at row " + u(v.row) + " (" + u(v.count_num) +
            " in num, " + u(v.count_den) + " in den)";
+}
+// the lines of a connection report under its product's calculateZ line
+inline std::string conn_lines(const zkgpu_conn_report &r, const std::vector<std::string> *labels)
+{
+    const auto pol = [&](uint32_t i) {
+        return labels && i < labels->size() && !(*labels)[i].empty() ? (*labels)[i] : "pols[" + u(i) + "]";
+    };
+    const auto link = [&](const zkgpu_conn_break &b) {
+        return pol(b.col) + " row " + u(b.row) + " (= " + u(b.value) + ") is wired to " + pol(b.to_col) + " row " +
+               u(b.to_row) + " (= " + u(b.to_value) + ")";
+    };
+    const std::string head = "  connection: ";
+    std::string s;
+    uint64_t listed = 0;
+    while (listed < ZKGPU_CONN_MAX && listed < r.n_broken && r.breaks[listed].row != UINT64_MAX) listed++;
+    if (r.n_broken) {
+        s += head + u(r.n_broken) + " cell(s) differ from the cell they are wired to";
+        if (listed) s += "; " + link(r.breaks[0]);
+        s += "\n";
+        for (uint64_t e = 1; e < listed; e++) s += head + link(r.breaks[e]) + "\n";
+        if (listed && r.n_broken > listed) s += head + "and " + u(r.n_broken - listed) + " more\n";
+    }
+    listed = 0;
+    while (listed < ZKGPU_CONN_MAX && listed < r.n_foreign && r.foreign[listed].row != UINT64_MAX) listed++;
+    if (r.n_foreign) {
+        s += head + u(r.n_foreign) + " cell(s) of S hold no cell's identity (a damaged or mismatched constant file)";
+        if (listed) s += "; S of " + pol(r.foreign[0].col) + " row " + u(r.foreign[0].row) + " holds " + u(r.foreign[0].s_value);
+        s += "\n";
+        for (uint64_t e = 1; e < listed; e++)
+            s += head + "S of " + pol(r.foreign[e].col) + " row " + u(r.foreign[e].row) + " holds " +
+                 u(r.foreign[e].s_value) + "\n";
+        if (listed && r.n_foreign > listed) s += head + "and " + u(r.n_foreign - listed) + " more\n";
+    }
+    if (r.n_untargeted)
+        s += head + u(r.n_untargeted) + " cell(s) are named by no S value: S is not a permutation of the cells\n";
+    if (!r.n_broken && !r.n_foreign && !r.n_untargeted)
+        s += head + "every cell holds the value of the cell it is wired to and S names every cell once; the wiring "
+                    "is not what keeps the product open\n";
+    return s;
 }
 }  // namespace audit_detail
 
@@ -83,6 +128,8 @@ inline std::string audit_format(const zkgpu_audit_report &r, const AuditContext 
             s += "; it follows from the misses of plookup " + u((uint64_t)c.z_plookup[z.z]) +
                  " (its h1 / h2 were zeroed)";
         s += "\n";
+        if (k < c.conn.size() && c.conn[k].ran)
+            s += audit_detail::conn_lines(c.conn[k], z.z < c.conn_col_label.size() ? &c.conn_col_label[z.z] : nullptr);
     }
     if (r.n_z_open > n_z_listed) s += "and " + u(r.n_z_open - n_z_listed) + " more open grand product(s)\n";
     if (r.n_pu_bad && r.n_z_open && c.z_plookup.empty())

@@ -119,6 +119,9 @@ _SIGS = {
     "zkgpu_multiset_diff_dev": (ctypes.c_int, [vp, vp, u64, vp, u64, u64, u32, u32]),
     "zkgpu_lookup_misses_workspace_bytes": (u64, [u64]),
     "zkgpu_lookup_misses_dev": (ctypes.c_int, [vp, vp, u64, vp, u64, u64, u32, u32]),
+    "zkgpu_conn_breaks_workspace_bytes": (u64, [u64, u32]),
+    "zkgpu_conn_ks_check": (ctypes.c_int, [vp, u32, u32]),
+    "zkgpu_conn_breaks_dev": (ctypes.c_int, [vp, vp, u64, vp, vp, u64, vp, u32, vp, u32, u32]),
     "zkgpu_h1h2_shard_route": (ctypes.c_int, [vp, u64, vp, vp, vp, u64, vp, u64, u64, u64, u32, u32]),
     "zkgpu_h1h2_shard_owner": (ctypes.c_int, [vp, vp, u64, u32, pu64]),
     "zkgpu_h1h2_shard_counts": (ctypes.c_int, [vp, vp, pu64, vp, vp, u64, u64, u64]),
@@ -903,6 +906,58 @@ def lookup_misses(f, t, max_vals=16):
     w = from_device(d_out)
     pairs = [(int(w[2 + 2 * k]), int(w[3 + 2 * k])) for k in range(max_vals) if int(w[2 + 2 * k]) != 2**64 - 1]
     return int(w[0]), int(w[1]), pairs
+
+
+def conn_breaks_workspace_bytes(n, k):
+    """device scratch bytes of conn_breaks_dev at n rows and k columns (no GPU needed)"""
+    return int(lib().zkgpu_conn_breaks_workspace_bytes(n, k))
+
+
+def _u32_list(v):
+    return None if v is None else np.ascontiguousarray(v, dtype=np.uint32)
+
+
+def conn_ks_check(ks, k, n_bits):
+    """raises ZkgpuError where conn_breaks_dev would refuse k, n_bits or the
+    coset shifts ks (None: 12^i) (zkgpu_conn_ks_check; no GPU needed)"""
+    ks = None if ks is None else _np(ks)
+    _check(lib().zkgpu_conn_ks_check(_addr(ks), k, n_bits), "zkgpu_conn_ks_check")
+
+
+def conn_breaks_dev(out, a, a_ld, a_cols, s, s_ld, s_cols, k, ks, n_bits, max_vals):
+    """out (device, 3 + 6 * max_vals words): the broken, foreign and
+    untargeted cells of the connection {a[a_cols]} connect {s[s_cols]} over
+    2^n_bits rows (column-major device sections, host column lists, None:
+    0 .. k-1; ks host coset shifts, None: 12^i), then max_vals records {cell,
+    target, value, value at target} and max_vals records {cell, S value}
+    (zkgpu_conn_breaks_dev; queued on the library stream)"""
+    a_cols, s_cols = _u32_list(a_cols), _u32_list(s_cols)
+    ks = None if ks is None else _np(ks)
+    _check(lib().zkgpu_conn_breaks_dev(_addr(out), _addr(a), a_ld, _addr(a_cols), _addr(s), s_ld, _addr(s_cols), k,
+                                       _addr(ks), n_bits, max_vals), "zkgpu_conn_breaks_dev")
+
+
+def conn_breaks(a, s, ks=None, max_vals=16):
+    """host columns a, s ((k, n) uint64, n a power of two) -> ((n_broken,
+    n_foreign, n_untargeted), [(cell, target, value, value at target)],
+    [(cell, S value)]): conn_breaks_dev through device copies"""
+    a, s = (np.ascontiguousarray(np.atleast_2d(np.asarray(c, dtype=np.uint64))) for c in (a, s))
+    if a.shape != s.shape or a.ndim != 2:
+        raise ValueError("a and s must have the same shape (k, n)")
+    k, n = a.shape
+    n_bits = n.bit_length() - 1
+    if n != 1 << n_bits:
+        raise ValueError("n must be a power of two")
+    d_a, d_s = to_device(a.ravel()), to_device(s.ravel())
+    d_out = to_device(np.zeros(3 + 6 * max_vals, np.uint64))
+    conn_breaks_dev(d_out, d_a, n, None, d_s, n, None, k, ks, n_bits, max_vals)
+    synchronize()
+    w = [int(x) for x in from_device(d_out)]
+    none = 2**64 - 1
+    breaks = [tuple(w[3 + 4 * e:7 + 4 * e]) for e in range(max_vals) if w[3 + 4 * e] != none]
+    f0 = 3 + 4 * max_vals
+    foreign = [tuple(w[f0 + 2 * e:f0 + 2 * e + 2]) for e in range(max_vals) if w[f0 + 2 * e] != none]
+    return tuple(w[:3]), breaks, foreign
 
 
 # calculateH1H2 over row-sharded f / t (include/zkgpu.h zkgpu_h1h2_shard_*;

@@ -109,6 +109,41 @@ class AuditReport(ctypes.Structure):
                 ("identities", CheckResult)]
 
 
+CONN_MAX = 16  # ZKGPU_CONN_MAX
+
+
+class ConnDesc(ctypes.Structure):
+    """zkgpu_conn_desc (include/zkgpu_stark.h)"""
+    _fields_ = [("k", ctypes.c_uint32), ("cm1_cols", ctypes.c_void_p), ("const_cols", ctypes.c_void_p),
+                ("ks", ctypes.c_void_p)]
+
+
+class ConnBreak(ctypes.Structure):
+    """zkgpu_conn_break (include/zkgpu_stark.h)"""
+    _fields_ = [("col", ctypes.c_uint32), ("to_col", ctypes.c_uint32), ("row", ctypes.c_uint64),
+                ("to_row", ctypes.c_uint64), ("value", ctypes.c_uint64), ("to_value", ctypes.c_uint64)]
+
+
+class ConnForeign(ctypes.Structure):
+    """zkgpu_conn_foreign (include/zkgpu_stark.h)"""
+    _fields_ = [("col", ctypes.c_uint32), ("row", ctypes.c_uint64), ("s_value", ctypes.c_uint64)]
+
+
+class ConnReport(ctypes.Structure):
+    """zkgpu_conn_report (include/zkgpu_stark.h)"""
+    _fields_ = [("ran", ctypes.c_uint32), ("z", ctypes.c_uint32), ("n_broken", ctypes.c_uint64),
+                ("n_foreign", ctypes.c_uint64), ("n_untargeted", ctypes.c_uint64), ("breaks", ConnBreak * CONN_MAX),
+                ("foreign", ConnForeign * CONN_MAX)]
+
+
+def _conn_dict(r):
+    return {"ran": int(r.ran), "z": int(r.z), "n_broken": int(r.n_broken), "n_foreign": int(r.n_foreign),
+            "n_untargeted": int(r.n_untargeted),
+            "breaks": [(int(b.col), int(b.row), int(b.to_col), int(b.to_row), int(b.value), int(b.to_value))
+                       for b in r.breaks if r.ran and b.row != 2**64 - 1],
+            "foreign": [(int(f.col), int(f.row), int(f.s_value)) for f in r.foreign if r.ran and f.row != 2**64 - 1]}
+
+
 _slib = None
 
 
@@ -146,6 +181,9 @@ def slib():
             ("zkgpu_stark_z_diag", ctypes.c_int, [vp, ctypes.POINTER(ZDiag)]),
             ("zkgpu_stark_audit", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.POINTER(AuditReport)]),
             ("zkgpu_stark_audit_format", ctypes.c_int, [vp, ctypes.c_char_p, u64]),
+            ("zkgpu_stark_conn_set", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.POINTER(ConnDesc)]),
+            ("zkgpu_stark_conn_check", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.POINTER(ConnReport)]),
+            ("zkgpu_stark_audit_conn", ctypes.c_int, [vp, ctypes.c_uint32, ctypes.POINTER(ConnReport)]),
             ("zkgpu_stark_check_names_set", ctypes.c_int, [vp, ctypes.c_int]),
             ("zkgpu_stark_check_terms", ctypes.c_int, [vp, vp, ctypes.c_uint32, vp]),
             ("zkgpu_stark_check_named", ctypes.c_int, [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp]),
@@ -587,6 +625,41 @@ class GpuStark:
         if n < 0:
             _check(n, "zkgpu_stark_audit_format")
         return buf.value.decode()
+
+    def conn_set(self, z, cm1_cols=None, const_cols=None, ks=None):
+        """declare grand product z (index into z_ctx) as the connection
+        {cm1_cols} connect {const_cols} with coset shifts ks (None: 12^i);
+        cm1_cols = None clears the declaration (zkgpu_stark_conn_set)"""
+        if cm1_cols is None:
+            _check(slib().zkgpu_stark_conn_set(self.h, z, None), "zkgpu_stark_conn_set")
+            return
+        a = np.ascontiguousarray(cm1_cols, dtype=np.uint32)
+        c = np.ascontiguousarray(const_cols, dtype=np.uint32)
+        if a.shape != c.shape or a.ndim != 1:
+            raise ValueError("cm1_cols and const_cols must be lists of one length")
+        k = None if ks is None else np.ascontiguousarray(ks, dtype=np.uint64)
+        if k is not None and k.shape != a.shape:
+            raise ValueError("ks must have one value per column")
+        d = ConnDesc(len(a), a.ctypes.data, c.ctypes.data, None if k is None else k.ctypes.data)
+        _check(slib().zkgpu_stark_conn_set(self.h, z, ctypes.byref(d)), "zkgpu_stark_conn_set")
+
+    def conn_check(self, z):
+        """the cells of the loaded trace that the declared connection z
+        leaves unequal, no stage program and no challenge
+        (zkgpu_stark_conn_check): dict(ran, z, n_broken, n_foreign,
+        n_untargeted, breaks [(col, row, to_col, to_row, value, to_value)],
+        foreign [(col, row, S value)]); col indexes the declared lists"""
+        r = ConnReport()
+        _check(slib().zkgpu_stark_conn_check(self.h, z, ctypes.byref(r)), "zkgpu_stark_conn_check")
+        return _conn_dict(r)
+
+    def audit_conn(self, k):
+        """the connection report that goes with entry k of the last audit's
+        open products, as conn_check; ran = 0 when there is none
+        (zkgpu_stark_audit_conn)"""
+        r = ConnReport()
+        _check(slib().zkgpu_stark_audit_conn(self.h, k, ctypes.byref(r)), "zkgpu_stark_audit_conn")
+        return _conn_dict(r)
 
     def check_names_set(self, on=True):
         """naming of every later checked proof (zkgpu_stark_check_names_set):

@@ -19,7 +19,8 @@ Committed polynomial order (cm_n / cm_2ns): the cm1 columns, then h1 / h2 of
 each plookup, then the Z of each plookup and of each permutation context (the
 instance's permutation checks first, peCtx[0 ..), then its h products) --
 the positions transposeH1H2Columns / transposeZColumns read (starks.cpp:14,
-406-520) -- then the other stage-2/3 columns and the quotient pieces.
+406-520) -- and of each connection check (ciCtx), then the other stage-2/3
+columns and the quotient pieces.
 """
 import json
 import os
@@ -88,6 +89,9 @@ def _committed_order(b, inst):
         b.committed("cm3_n", pe["z"], 3)
     for j in range(inst.m):
         b.committed("cm3_n", inst.z_ctx[j][2], 3)
+    # then ciCtx: the connection checks
+    for cn in inst.conns:
+        b.committed("cm3_n", cn["z"], 3)
     for j in range(inst.m):
         b.committed("cm2_n", 3 * j, 3)
     if inst.with_step3:
@@ -153,6 +157,8 @@ def starkinfo(inst):
            "denId": b.exp(q["den"], 3), "c2Id": 0} for q in inst.perms]
     pe += [{"tExpId": 0, "fExpId": 0, "zId": 0, "c1Id": 0, "numId": b.exp(inst.z_ctx[j][0], 3),
             "denId": b.exp(inst.z_ctx[j][1], 3), "c2Id": 0} for j in range(inst.m)]
+    ci = [{"zId": 0, "numId": b.exp(cn["num"], 3), "denId": b.exp(cn["den"], 3), "c1Id": 0, "c2Id": 0}
+          for cn in inst.conns]
     qs = [b.pol("cm4_2ns", 3 * p, 3) for p in range(inst.q_deg)]
     ev = []
     for sec, col, dim, prime in inst.evmap:
@@ -181,7 +187,7 @@ def starkinfo(inst):
         "cm_2ns": b.cm_2ns,
         "peCtx": pe,
         "puCtx": pu,
-        "ciCtx": [],
+        "ciCtx": ci,
         "evMap": ev,
         "starkStruct": {"nBits": inst.n_bits, "nBitsExt": inst.n_bits_ext, "nQueries": inst.n_queries,
                         "verificationHashType": "GL", "steps": [{"nBits": s} for s in inst.fri_steps]},
@@ -237,6 +243,20 @@ def write_inputs(d, inst, const_rows, const_2ns_rows, const_nodes, cm1_rows, pub
     path = os.path.join(d, "config.json")
     with open(path, "w") as f:
         json.dump(cfg, f, indent=4)
+    return path
+
+
+def connections(inst):
+    """the driver's --connections sidecar of the instance: per ciCtx entry the cm1 columns it connects,
+    the constant columns that hold the wiring and the coset shifts (the starkinfo carries only
+    expression ids under ciCtx)"""
+    return [{"ciCtx": i, "pols": list(cn["cols"]), "S": list(cn["S"]), "ks": [str(k) for k in cn["ks"]]}
+            for i, cn in enumerate(inst.conns)]
+
+
+def write_connections(path, inst):
+    with open(path, "w") as f:
+        json.dump(connections(inst), f, indent=1)
     return path
 
 

@@ -28,7 +28,16 @@ Starks::genProof (starks.cpp:9-404):
              permutation: f = A + u B, t = C + u D (stage 2, tmpExp, dim 3),
              num = f + gamma, den = t + gamma (step3prev), Z their grand
              product: it closes exactly when the tuples of (A, B) and (C, D)
-             are the same multiset
+             are the same multiset;
+             connection (n_conns, 0 by default): conn_k cm1 columns a_0 (random),
+             a_{i+1}[r] = a_0[r + rot_0 + .. + rot_i] (step1) against conn_k
+             constants S_i (step0, from x): cell (i, r) has the identity
+             ks[i] w^r, ks[i] = 12^i, and S_i[r] is the identity of the cell it
+             is wired to -- (i + 1, r) to (i, r + rot_i), (0, r) to (k - 1,
+             r + rot_{k-1}), the rotations summing to 0 mod n -- so
+             num = prod_i (a_i + beta ks[i] x + gamma),
+             den = prod_i (a_i + beta S_i + gamma) (step3prev), and Z closes
+             exactly when every cell holds the value of the cell it is wired to
   stage 4    alpha = ch[4]; C = Horner_alpha of all constraints; q = C / Z_H
              (step42ns semantics, op 69), split into qDeg = 2 pieces (cm4, 6 cols)
   stage 5    xi = ch[7]; evals (evmap); v1 = ch[5], v2 = ch[6];
@@ -119,7 +128,7 @@ class Program:
 class SyntheticStark:
     def __init__(self, n_bits=10, blowup_bits=1, t=4, m=2, n_k=3, n_queries=16, fri_steps=None, n_publics=8,
                  seed=0x5EED, n_free=0, n_lookups=2, q_deg=2, with_step3=True, n_free2=0, n_free3=0, n_free_tmp=0,
-                 n_perms=0):
+                 n_perms=0, n_conns=0, conn_k=2):
         self.n_bits = n_bits
         self.n_bits_ext = n_bits + blowup_bits
         self.blowup_bits = blowup_bits
@@ -139,6 +148,16 @@ class SyntheticStark:
         self.n_perms = n_perms
         self.perms = [{"cols": list(range(self.n_cm1 + 4 * k, self.n_cm1 + 4 * k + 4))} for k in range(n_perms)]
         self.n_cm1 += 4 * n_perms
+        # connection checks: conn_k cm1 columns and conn_k constants S each, after everything else
+        assert n_conns == 0 or 1 <= conn_k <= q_deg, "a connection of k columns has degree k + 1"
+        self.n_conns, self.conn_k = n_conns, conn_k
+        self.conns = []
+        for _ in range(n_conns):
+            self.conns.append({"cols": list(range(self.n_cm1, self.n_cm1 + conn_k)),
+                               "S": list(range(self.n_const, self.n_const + conn_k)),
+                               "ks": [pow(12, i, P) for i in range(conn_k)], "rot": self.conn_rotations(conn_k)})
+            self.n_cm1 += conn_k
+            self.n_const += conn_k
         # plookup contexts: dim, f/t tmp cols, h1/h2 cm2 cols, num/den tmp cols, Z cm3 col
         self.lookups = []
         cm2, tmp, cm3 = 3 * m, 6 * m, 3 * m
@@ -154,6 +173,10 @@ class SyntheticStark:
         for pe in self.perms:
             pe.update({"f": tmp, "t": tmp + 3, "num": tmp + 6, "den": tmp + 9, "z": cm3})
             tmp += 12
+            cm3 += 3
+        for cn in self.conns:
+            cn.update({"num": tmp, "den": tmp + 3, "z": cm3})
+            tmp += 6
             cm3 += 3
         self.cm2_free = list(range(cm2, cm2 + n_free2))
         self.n_cm2 = cm2 + n_free2
@@ -188,6 +211,7 @@ class SyntheticStark:
         self.z_ctx = [(6 * j, 6 * j + 3, 3 * j) for j in range(m)]  # (num tmp col, den tmp col, z cm3 col)
         self.z_ctx += [(lk["num"], lk["den"], lk["z"]) for lk in self.lookups]
         self.z_ctx += [(pe["num"], pe["den"], pe["z"]) for pe in self.perms]
+        self.z_ctx += [(cn["num"], cn["den"], cn["z"]) for cn in self.conns]
         self.pu = [(lk["f"], lk["t"], lk["h1"], lk["h2"], lk["dim"]) for lk in self.lookups]
         self._build_evmap()
         self.programs = {
@@ -227,6 +251,9 @@ class SyntheticStark:
         for pe in self.perms:
             ev.append((SEC_CM3_2NS, pe["z"], 3, 0))
             ev.append((SEC_CM3_2NS, pe["z"], 3, 1))
+        for cn in self.conns:
+            ev.append((SEC_CM3_2NS, cn["z"], 3, 0))
+            ev.append((SEC_CM3_2NS, cn["z"], 3, 1))
         if self.with_step3:
             ev.append((SEC_CM3_2NS, self.cm3_w, 3, 0))
         for j, c in enumerate(self.cm2_free):
@@ -242,17 +269,39 @@ class SyntheticStark:
 
     # ------------------------------------------------------------ programs
     def _prog_step0(self):
-        """Constant derivation (setup): T2 = T0 with row 0 := T0[N/2]."""
+        """Constant derivation (setup): T2 = T0 with row 0 := T0[N/2]; the
+        connections' S_i = (identity of the cell (i, r) is wired to) = c_i x."""
         p = Program(0)
-        if len(self.c_t) < 3:
-            return p
-        t = p.tmp1()
-        t0, lf = p.col(SEC_CONST_N, self.c_t[0]), p.col(SEC_CONST_N, self.l_first)
-        p.op(SUB, t, p.col(SEC_CONST_N, self.c_t[0], 1 << (self.n_bits - 1)), t0)
-        p.op(MUL, t, t, lf)
-        p.op(ADD, t, t, t0)
-        p.op(COPY, p.col(SEC_CONST_N, self.c_t[2]), t)
+        if len(self.c_t) >= 3:
+            t = p.tmp1()
+            t0, lf = p.col(SEC_CONST_N, self.c_t[0]), p.col(SEC_CONST_N, self.l_first)
+            p.op(SUB, t, p.col(SEC_CONST_N, self.c_t[0], 1 << (self.n_bits - 1)), t0)
+            p.op(MUL, t, t, lf)
+            p.op(ADD, t, t, t0)
+            p.op(COPY, p.col(SEC_CONST_N, self.c_t[2]), t)
+        for cn in self.conns:
+            for i, c in enumerate(self.conn_s_factors(cn)):
+                p.op(MUL, p.col(SEC_CONST_N, cn["S"][i]), p.lit(c), p.o(X))
         return p
+
+    @staticmethod
+    def conn_rotations(k):
+        """rot_i, i < k - 1 (the last one closes the cycle: conn_wiring)"""
+        return [3 + 2 * i for i in range(k - 1)]
+
+    def conn_wiring(self, cn):
+        """[(target column index, row rotation)] by column index: cell (i, r)
+        is wired to cell (j, r + rot mod n)"""
+        k, n = len(cn["cols"]), 1 << self.n_bits
+        rot = cn["rot"]
+        return [(k - 1, -sum(rot) % n)] + [(i, rot[i]) for i in range(k - 1)]
+
+    def conn_s_factors(self, cn):
+        """c_i with S_i = c_i x: ks[target column] w^rot"""
+        w = 7277203076849721926  # of order 2^32
+        for _ in range(self.n_bits, 32):
+            w = w * w % P
+        return [cn["ks"][j] * pow(w, r, P) % P for j, r in self.conn_wiring(cn)]
 
     # rows of the tables the lookup columns read: A, B at T[i+5] (row 0: T[11]), C at T2[i+7]
     LK_SHIFT, LK_SHIFT0, LK_SHIFT_C = 5, 11, 7
@@ -284,7 +333,30 @@ class SyntheticStark:
             a, b, c, d = pe["cols"]
             p.op(COPY, p.col(SEC_CM1_N, c), p.col(SEC_CM1_N, a, self.PERM_ROT))
             p.op(COPY, p.col(SEC_CM1_N, d), p.col(SEC_CM1_N, b, self.PERM_ROT))
+        # a_{i+1}[r] = a_i[r + rot_i], read from the random a_0 (no column is read and written here)
+        for cn in self.conns:
+            for i in range(len(cn["cols"]) - 1):
+                p.op(COPY, p.col(SEC_CM1_N, cn["cols"][i + 1]),
+                     p.col(SEC_CM1_N, cn["cols"][0], sum(cn["rot"][:i + 1])))
         return p
+
+    def _emit_conn_num_den(self, p, cn, cm1_sec, const_sec):
+        """(num, den) temps of a connection: prod_i (a_i + beta ks[i] x + gamma),
+        prod_i (a_i + beta S_i + gamma)"""
+        gamma, beta = p.chal(2), p.chal(3)
+        num, den, f, idx = p.tmp3(), p.tmp3(), p.tmp3(), p.tmp1()
+        for i, c in enumerate(cn["cols"]):
+            a = p.col(cm1_sec, c)
+            p.op(MUL, idx, p.lit(cn["ks"][i]), p.o(X))
+            for acc, ident in ((num, idx), (den, p.col(const_sec, cn["S"][i]))):
+                p.op(MUL, f, beta, ident)
+                p.op(ADD, f, f, a)
+                if i == 0:
+                    p.op(ADD, acc, f, gamma)
+                else:
+                    p.op(ADD, f, f, gamma)
+                    p.op(MUL, acc, acc, f)
+        return num, den
 
     def _pe_ft(self, p, pe, cm1_sec):
         """(f, t) temps of a permutation check: f = A + u B, t = C + u D."""
@@ -397,6 +469,10 @@ class SyntheticStark:
         for pe in self.perms:
             p.op(ADD, p.col3(SEC_TMP_N, pe["num"]), p.col3(SEC_TMP_N, pe["f"]), gamma)
             p.op(ADD, p.col3(SEC_TMP_N, pe["den"]), p.col3(SEC_TMP_N, pe["t"]), gamma)
+        for cn in self.conns:
+            num, den = self._emit_conn_num_den(p, cn, SEC_CM1_N, SEC_CONST_N)
+            p.op(COPY, p.col3(SEC_TMP_N, cn["num"]), num)
+            p.op(COPY, p.col3(SEC_TMP_N, cn["den"]), den)
         # tmpExp fillers: (cm2 filler)' + a
         for j, c in enumerate(self.tmp_free):
             src = (p.col(SEC_CM2_N, self.cm2_free[j % len(self.cm2_free)], 1) if self.cm2_free
@@ -513,6 +589,21 @@ class SyntheticStark:
                 return t
             out.append(c_pe_first)
             out.append(c_pe_z)
+        for cn in self.conns:
+            def c_cn_first(cn=cn):
+                r = p.tmp3()
+                p.op(SUB, r, p.col3(SEC_CM3_2NS, cn["z"]), p.lit(1))
+                p.op(MUL, r, r, p.col(SEC_CONST_2NS, self.l_first))
+                return r
+
+            def c_cn_z(cn=cn):
+                num, den = self._emit_conn_num_den(p, cn, SEC_CM1_2NS, SEC_CONST_2NS)
+                p.op(MUL, den, den, p.col3(SEC_CM3_2NS, cn["z"], nxt))
+                p.op(MUL, num, num, p.col3(SEC_CM3_2NS, cn["z"]))
+                p.op(SUB, den, den, num)
+                return den
+            out.append(c_cn_first)
+            out.append(c_cn_z)
         return out
 
     def _prog_step42ns(self):
@@ -541,6 +632,7 @@ class SyntheticStark:
         cols += [(SEC_CM3_2NS, 3 * j, 3) for j in range(self.m)]
         cols += [(SEC_CM3_2NS, lk["z"], 3) for lk in self.lookups]
         cols += [(SEC_CM3_2NS, pe["z"], 3) for pe in self.perms]
+        cols += [(SEC_CM3_2NS, cn["z"], 3) for cn in self.conns]
         if self.with_step3:
             cols += [(SEC_CM3_2NS, self.cm3_w, 3)]
         cols += [(SEC_CM2_2NS, c, 1) for c in self.cm2_free]
@@ -607,7 +699,7 @@ class SyntheticStark:
 
     def random_cm1_cols(self):
         return ([c for c in range(3 * self.t + self.n_free) if c >= 3 * self.t or c % 3 != 2] +
-                [c for pe in self.perms for c in pe["cols"][:2]])
+                [c for pe in self.perms for c in pe["cols"][:2]] + [cn["cols"][0] for cn in self.conns])
 
     def random_const_cols(self):
         """K_k and the random tables T0, T1 (T2 is derived by step0)."""
