@@ -32,6 +32,7 @@
 
 #include "../../include/zkgpu.h"
 #include "../../include/zkgpu_stark.h"
+#include "../../zkevm-prover_amd/host/host_error.hpp"  // g_err, as the exchange's fail() leaves it
 
 extern "C" int zkgpu_memcpy_d2h(void *dst, const void *src, uint64_t bytes)
 {
@@ -46,15 +47,6 @@ extern "C" int zkgpu_memcpy_h2d(void *dst, const void *src, uint64_t bytes)
 extern "C" const char *zkgpu_last_error(void) { return "(host memcpy)"; }
 
 namespace zkgpu_host {
-static char g_err[512];
-static int fail(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return -1;
-}
 static int g_slow_rank = -1;  // this rank sleeps between barrier 2 and the flag read
 }  // namespace zkgpu_host
 

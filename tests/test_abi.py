@@ -29,7 +29,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_stark_library_exports_every_declared_symbol():
-    """include/zkgpu_stark.h is libzkgpu_stark.so (host/starks.cpp)."""
+    """include/zkgpu_stark.h is libzkgpu_stark.so (host/starks_abi.cpp)."""
     import zkgpu
     from zkgpu import stark
     L = ctypes.CDLL(stark.STARK_LIB)

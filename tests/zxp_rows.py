@@ -6,7 +6,7 @@ eval_rows    one program on the rows its before-records reach (numpy object
 check_probe  every program point of a probe: evaluate from the before-records
              and scalars, compare every stored column with the after-record
 oracle_probe the same records from oracle.stark_prover.OracleStark
-plan         the record list a probe has (the rule of host/starks.cpp probe_set)
+plan         the record list a probe has (the rule of host/starks_diag.cpp Probe::set)
 
 Conventions as oracle/stark.c zxp_run: temporaries are zero at the start of a
 row, F_p^3 (+/-) F_p touches component 0, a store canonicalises, a base value

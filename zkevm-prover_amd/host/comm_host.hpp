@@ -1,5 +1,5 @@
-// zkgpu_comm through host shared memory between the processes of one machine;
-// included by starks.cpp.  For ranks that cannot use RCCL -- several
+// zkgpu_comm through host shared memory between the processes of one machine
+// (included by starks_abi.cpp).  For ranks that cannot use RCCL -- several
 // processes sharing one GPU (the multi-rank tests of the C++ driver), or a
 // machine without xGMI peers.  Every rank owns an outbox in a POSIX shared
 // memory segment: an exchange copies the rank's send slices into its outbox
@@ -14,7 +14,9 @@
 // aborts (zkgpu_comm.abort: its proof failed), marks the segment broken and
 // every rank's next wait fails -- a failed or stopped rank cannot leave its
 // peers waiting forever.
+#pragma once
 #include <fcntl.h>
+#include <string.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -24,6 +26,10 @@
 #include <cstdlib>
 #include <string>
 #include <thread>
+#include <vector>
+
+#include "../../include/zkgpu_stark.h"
+#include "host_error.hpp"
 
 namespace zkgpu_host {
 

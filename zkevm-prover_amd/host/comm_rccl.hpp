@@ -1,5 +1,5 @@
 // zkgpu_comm over RCCL (xGMI between the GPUs of a node); included by
-// starks.cpp.  librccl is opened at run time, so the prover library carries
+// starks_abi.cpp.  librccl is opened at run time, so the prover library carries
 // no link dependency on it and a process that never shards never loads it.
 // One exchange = ncclSend / ncclRecv of every operation inside one
 // ncclGroupStart / ncclGroupEnd, enqueued on the zkgpu stream: RCCL matches
@@ -13,11 +13,12 @@
 // the communicator (ncclCommAbort: the transfer kernels see the abort flag and
 // exit) and fails, and every later exchange fails at once.  A rank whose proof
 // fails locally aborts through zkgpu_comm.abort (ShardedStarks::prove).
+#pragma once
 #include <dlfcn.h>
+#include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
-#include <chrono>
-#include <thread>
+#include "comm_host.hpp"  // comm_timeout_s, comm_wait
 
 namespace zkgpu_host {
 
@@ -60,8 +61,6 @@ struct RcclApi {
 };
 
 static RcclApi g_rccl;
-
-// (comm_timeout_s / comm_wait: comm_host.hpp, included first)
 
 struct RcclCtx {
     ncclComm_t comm = nullptr;

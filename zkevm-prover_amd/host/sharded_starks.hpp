@@ -1,5 +1,6 @@
 // ShardedStarks: ONE proof of one trace over the GPUs of a node, one process
-// per GPU (BASELINE configs[4]); included by starks.cpp.
+// per GPU (BASELINE configs[4]); included by
+// starks_abi.cpp, which makes such provers (zkgpu_stark_create_sharded).
 //
 // The reference proves on one host (Starks::genProof, starks.cpp:9-404).  Here
 // BOTH domains are partitioned by ROWS over W ranks, so no rank holds a whole
@@ -57,10 +58,17 @@
 // Every exchange is a zkgpu_comm call (RCCL over xGMI in production, see
 // comm_rccl.hpp; the tests plug a host-staged one); a rank never sends to
 // itself -- its own slices are device copies.
+#pragma once
+#include <stdio.h>
+
+#include "starks.hpp"
+
+namespace zkgpu_host {
 
 class ShardedStarks : public Starks
 {
 public:
+    ShardedStarks() : Starks(true) {}
     zkgpu_comm comm{};
     uint32_t W = 1, R = 0;
     uint64_t B = 0, H = 0, BH = 0;     // 2n domain: block rows, halo rows (2^blowup), ld (>= B + H)
@@ -222,27 +230,19 @@ public:
         const uint32_t widths_n[5] = {info.n_cm1, info.n_cm2, info.n_cm3, info.n_tmp, info.n_const};
         uint32_t wmax = 1;
         for (int s = 0; s < 5; s++) {
-            if (dalloc(&S.sec[s], (uint64_t)(widths_n[s] ? widths_n[s] : 1) * ldn)) return -1;
-            S.ld[s] = ldn;
-            S.ncols[s] = widths_n[s];
+            if (alloc_sec(s, widths_n[s], ldn)) return -1;
             wmax = std::max(wmax, widths_n[s]);
         }
         const uint32_t blk_secs[4] = {SEC_CM1_2NS, SEC_CM2_2NS, SEC_CM3_2NS, SEC_CONST_2NS};
         const uint32_t blk_w[4] = {info.n_cm1, info.n_cm2, info.n_cm3, info.n_const};
-        for (int k = 0; k < 4; k++) {
-            if (dalloc(&S.sec[blk_secs[k]], (uint64_t)(blk_w[k] ? blk_w[k] : 1) * BH)) return -1;
-            S.ld[blk_secs[k]] = BH;
-            S.ncols[blk_secs[k]] = blk_w[k];
-        }
+        for (int k = 0; k < 4; k++)
+            if (alloc_sec(blk_secs[k], blk_w[k], BH)) return -1;
         if (dalloc(&cm4, (uint64_t)(info.n_cm4 ? info.n_cm4 : 1) * NE)) return -1;
         S.sec[SEC_CM4_2NS] = cm4 + (uint64_t)R * B;
         S.ld[SEC_CM4_2NS] = NE;
         S.ncols[SEC_CM4_2NS] = info.n_cm4;
-        for (uint32_t s : {(uint32_t)SEC_Q_2NS, (uint32_t)SEC_F_2NS}) {
-            if (dalloc(&S.sec[s], 3 * B)) return -1;
-            S.ld[s] = B;
-            S.ncols[s] = 3;
-        }
+        for (uint32_t s : {(uint32_t)SEC_Q_2NS, (uint32_t)SEC_F_2NS})
+            if (alloc_sec(s, 3, B)) return -1;
         const uint64_t ms = max_share();
         // ext: the LDE of the share, and before it the transposes' receive
         // staging (W slots of ms x ldn words: more than ms x NE only for tiny
@@ -724,60 +724,8 @@ public:
         cm1_pending = true;
         return 0;
     }
-    int get_cm1(uint64_t *) override { return fail("stark (sharded): get_cm1 is single-GPU only"); }
-    int probe_set(const uint64_t *, uint32_t, const uint64_t *, uint32_t) override
-    {
-        return fail("stark (sharded): probe_set is single-GPU only (the sampled rows live on other ranks)");
-    }
-    int check_set(uint32_t) override
-    {
-        return fail("stark (sharded): check_set is single-GPU only (the n-domain sections live in row blocks on the "
-                    "ranks)");
-    }
-    int z_diag(zkgpu_z_diag *) const override
-    {
-        return fail("stark (sharded): z_diag: single-GPU provers only (a rank holds a row block of num and den)");
-    }
-    int audit(uint32_t, zkgpu_audit_report *) override
-    {
-        return fail("stark (sharded): audit: single-GPU provers only (a rank holds a row block of the n-domain "
-                    "sections)");
-    }
-    int audit_format(char *, uint64_t) const override
-    {
-        return fail("stark (sharded): audit_format: single-GPU provers only");
-    }
-    int conn_set(uint32_t, const zkgpu_conn_desc *) override
-    {
-        return fail("stark (sharded): conn_set: single-GPU provers only (as the audit)");
-    }
-    int conn_check(uint32_t, zkgpu_conn_report *) override
-    {
-        return fail("stark (sharded): conn_check: single-GPU provers only (a rank holds a row block of the n-domain "
-                    "sections)");
-    }
-    int audit_conn(uint32_t, zkgpu_conn_report *) const override
-    {
-        return fail("stark (sharded): audit_conn: single-GPU provers only");
-    }
-    int check_names_set(int) override
-    {
-        return fail("stark (sharded): check_names_set is single-GPU only (as check_set)");
-    }
-    int prove_from_rows(const uint64_t *, int, uint64_t *) override
-    {
-        return fail("stark (sharded): prove_from_rows is single-GPU only (each rank loads its rows: set_cm1 / "
-                    "set_cm1_async, then prove)");
-    }
-    int set_exec(const uint64_t *, uint64_t, uint64_t) override
-    {
-        return fail("stark (sharded): set_exec is single-GPU only (the recursion circuits' traces fit one device)");
-    }
-    int set_cm1_witness(const uint64_t *) override
-    {
-        return fail("stark (sharded): set_cm1_witness is single-GPU only (the recursion circuits' traces fit one "
-                    "device)");
-    }
+    // (the single-GPU entry points -- the diagnostics, prove_from_rows, the .exec hand-off, get_cm1 --
+    // never reach this class: starks_abi.cpp refuses a sharded handle)
     uint64_t stream_stage_words() const override { return 0; }
 
     // the executor's row-major buffer: the rank takes rows [r0, r0 + ldn) mod N
@@ -1166,13 +1114,7 @@ public:
                 for (uint32_t c = 0; c < d; c++) dst.push_back(3 * part + c);
             CK(zkgpu_copy_rows_dev(fw, N, r0(), dst.data(), S.sec[SEC_TMP_N], ldn, 0, 0, ft.data(), 2 * d, nb));
             uint64_t miss = 0;
-            const int rc = zkgpu_h1h2_dev(h1w, N, h2w, N, fw, N, tw, N, N, d, &miss);
-            if (rc) {
-                if (miss != ~0ULL)
-                    return fail("Polinomial::calculateH1H2() Number not included: w=%llu plookup_number=%u",
-                                (unsigned long long)miss, k);
-                return fail("calculateH1H2: %s", zkgpu_last_error());
-            }
+            if (zkgpu_h1h2_dev(h1w, N, h2w, N, fw, N, tw, N, N, d, &miss)) return h1h2_failed(k, miss);
             CK(zkgpu_copy_rows_dev(S.sec[SEC_CM2_N] + (uint64_t)q[2] * ldn, ldn, 0, nullptr, h1w, N, r0(), info.n_bits,
                                    nullptr, d, ldn));
             CK(zkgpu_copy_rows_dev(S.sec[SEC_CM2_N] + (uint64_t)q[3] * ldn, ldn, 0, nullptr, h2w, N, r0(), info.n_bits,
@@ -1296,3 +1238,5 @@ public:
         return 0;
     }
 };
+
+}  // namespace zkgpu_host
