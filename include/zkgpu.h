@@ -340,12 +340,21 @@ int zkgpu_zxp_eval_dev(const void *instr, uint32_t n_instr, const void *opnd, ui
  * quotient and FRI programs run on the rows a GPU owns after the column ->
  * row exchange).  Rows 0 .. 2^log_rows - 1 of every section are evaluated;
  * x_i = x_start * w_{2^log_domain}^i (x_start = 7 * w^row0 for a block
- * starting at global row row0), zhInv uses N = 2^(log_domain - extend_bits)
- * (row0 must be a multiple of 2^extend_bits), and a read at row shift s >= 0
- * does not wrap: the caller stores the next block's first s rows (the halo)
- * after the block, so every section's ld >= 2^log_rows + s.  A store at row
- * shift s likewise writes local row i + s: its last s rows land in the halo,
- * and the caller moves them to the next block (host/sharded_starks.hpp). */
+ * starting at global row row0), zhInv uses N = 2^(log_domain - extend_bits),
+ * and a read at row shift s >= 0 does not wrap: the caller stores the next
+ * block's first s rows (the halo) after the block, so every section's
+ * ld >= 2^log_rows + s.  A store at row shift s likewise writes local row
+ * i + s: its last s rows land in the halo, and the caller moves them to the
+ * next block (host/sharded_starks.hpp).
+ * The call takes x_start, not row0, so two things are the caller's duty and
+ * cannot be checked here.  The block must start at a multiple of
+ * 2^extend_bits: zhInv has 2^extend_bits entries and is indexed by the LOCAL
+ * row (i mod 2^extend_bits), which is the global row's entry only then.  And
+ * xdiv / xdivw are read at local row i (words 3 i .. 3 i + 2): the caller
+ * passes them advanced to the block's first row (base + 3 row0).
+ * ZKGPU_ERR_ARG, nothing queued: log_rows > log_domain, a read or store at a
+ * negative row shift, a section whose ld is below 2^log_rows + s for a column
+ * read or stored at shift s. */
 int zkgpu_zxp_eval_block_dev(const void *instr, uint32_t n_instr, const void *opnd, uint32_t n_opnd, uint32_t n_tmp1,
                              uint32_t n_tmp3, const zkgpu_sections *sections, uint32_t log_rows, uint32_t log_domain,
                              const uint64_t *challenges, const uint64_t *publics, uint32_t n_publics,

@@ -115,12 +115,14 @@ def plan(inst, rows_n, rows_ext):
     return out
 
 
-def eval_rows(prog, dom_bits, ext, eb, records_before, scalars, publics, rows=None):
+def eval_rows(prog, dom_bits, ext, eb, records_before, scalars, publics, rows=None, xdiv=None, xdivw=None):
     """Evaluate a ZXP source program on sampled rows.
 
     records_before: {section: (rows, vals (n_rows, ncols))}; scalars:
     challenges[24] then evals; rows: the rows to evaluate (default: every row
-    whose reads the records cover).  Returns {(section, column): (rows
+    whose reads the records cover); xdiv / xdivw: (rows, vals (n_rows, 3))
+    records of the caller's x/(x - xi), x/(x - w xi) arrays, read in place of
+    the values derived from challenge 7.  Returns {(section, column): (rows
     written, values)}: a store at shift s writes row (r + s) mod dom.
     Raises ValueError on a shifted read of a column the program itself stores
     (at another shift than the store's) and KeyError on a row the records lack."""
@@ -157,6 +159,13 @@ def eval_rows(prog, dom_bits, ext, eb, records_before, scalars, publics, rows=No
     w_dom, w_n = gl_w(dom_bits), gl_w(nb)
     x = np.array([(7 if ext else 1) * pow(w_dom, int(r), P) % P for r in R], dtype=object)
     lazy = {}
+    for kind, rec in ((XDIV, xdiv), (XDIVW, xdivw)):
+        if rec is not None:
+            rr, vals = np.asarray(rec[0], np.uint64).astype(np.int64), np.asarray(rec[1])
+            idx = np.searchsorted(rr, R.astype(np.int64))
+            if (idx >= rr.size).any() or (rr[np.minimum(idx, rr.size - 1)] != R.astype(np.int64)).any():
+                raise KeyError("a row is not in the xdiv record")
+            lazy[kind] = tuple(vals[idx, k].astype(object) for k in range(3))
 
     def special(kind):
         if kind not in lazy:

@@ -789,8 +789,19 @@ def zxp_jit_cached(prog, challenges, publics, evals=None):
 
 def zxp_eval_block_dev(prog, sections, log_rows, log_domain, challenges, publics, evals=None, xdiv=None, xdivw=None,
                        extend_bits=0, x_start=7):
-    """One row block of a row-sharded domain (zkgpu_zxp_eval_block_dev):
-    sections carry the block plus halo rows; x_start = 7 * w^row0."""
+    """One row block of a row-sharded domain (zkgpu_zxp_eval_block_dev): rows
+    0 .. 2^log_rows - 1 of every section are evaluated, x_i = x_start w^i
+    with w of order 2^log_domain (x_start = w^row0 on the trace domain,
+    7 w^row0 on the extended one).  sections: {index: (tensor or address, ld,
+    ncols)} of the block's local image.  Nothing wraps: a read at row shift
+    s >= 0 takes local row i + s, so behind the block's rows every section
+    carries the halo, the next block's first s rows (the domain's first rows
+    after the last block), and ld >= 2^log_rows + s; a store at shift s
+    writes local rows s .. 2^log_rows + s - 1, the last s of them in the halo
+    (the caller hands them on).  A negative shift or a shorter ld is refused.
+    xdiv / xdivw are passed already advanced to the block (the whole array's
+    address + 24 row0 bytes), and row0 must be a multiple of 2^extend_bits:
+    zhInv is indexed by the local row."""
     ins, opn = prog.arrays()
     ins = np.ascontiguousarray(ins, np.uint32)
     opn = np.ascontiguousarray(opn, np.uint32)
